@@ -1,7 +1,18 @@
 """Benchmark of the MI355X-native SGM hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config c3|c2|c5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, K timed
+steps, the result line (with the per-stage HIP-event times and the roofline of the timed region
+itself). `--full` adds every measurement that takes a run of its own: the device-to-device copy
+rate beside the roofline, the `single_frame` latency, the `c5` block and, at N = 1, the
+`cpu_baseline` (each can still be left out with `--no-c5` / `--no-cpu-baseline`).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last
+step as float32 `DIR/<name>.npy` (see dump_outputs). The inputs are seeded synthetic frames, so
+the same arguments give the same inputs in every run and two builds compare output for output.
 
 `--gpus N` alone (no WORLD_SIZE in the environment) starts the N rank processes itself, before
 this process makes any GPU call (one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
@@ -19,14 +30,15 @@ only collectives are the timing barrier and the max-over-ranks reduction.
 
 `roofline` is the dominant kernel (algorithmic bytes / its average HIP-event duration over
 the timed region); `pipeline` is the whole frame (SURVEY §8d B_alg / per-frame device
-time). `cpu_baseline` times the CPU port (oracle) on a bounded sample on rank 0 at N = 1.
+time). `cpu_baseline` (`--full`) times the CPU port (oracle) on a bounded sample on rank 0 at
+N = 1.
 
 C5 (BASELINE configs[4], 4096x3000 D=512, one frame): `--config c5` times it on its own — at
 N = 1 the single-device full frame (sgm_match_device), at N > 1 the overlap tile mode
 (sgm_match_tiled_device: N row bands + 128-row halos, one band per GPU, rows moved over xGMI)
 driven by one process (rank 0 under torchrun, the other ranks wait at a barrier) — and reports
-the disagreement with the 1-GPU full frame. The default C3 run adds the same measurement as
-its `c5` block (a child process after the C3 timed region, while the other ranks wait).
+the disagreement with the 1-GPU full frame. The C3 run with `--full` adds the same measurement
+as its `c5` block (a child process after the C3 timed region, while the other ranks wait).
 """
 import argparse
 import json
@@ -89,6 +101,39 @@ def load_pmc_traffic(config):
         return json.load(open(path))
     except Exception:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000    # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 8 * 1000 * 1000          # elements of the seeded sample of a larger output
+
+
+def dump_outputs(dirpath, disp, seed=0):
+    """--dump-outputs: the disparity maps of the last timed step, `disp` = the int16 output
+    buffer(s) the caller of the timed path receives ([frames,] H, W; 16 x disparity, invalid
+    pixels (minD - 1) * 16), written as float32 (exact for int16). An output within the size
+    limit is written whole as `disparity.npy`. A larger one (the 64-frame batch) is written as
+    its first and last frame (`disparity_first_frame.npy`, `disparity_last_frame.npy`) and
+    `disparity_sample.npy`: the elements of the flattened buffer at the sorted indices
+    numpy.random.default_rng(seed).integers(0, size, DUMP_SAMPLE), the same in every run.
+    Returns {name: shape}."""
+    import numpy as np
+    if isinstance(disp, (list, tuple)):
+        a = np.stack([np.asarray(d) for d in disp])
+    else:
+        a = disp.cpu().numpy() if hasattr(disp, "cpu") else np.asarray(disp)
+    os.makedirs(dirpath, exist_ok=True)
+    files = {}
+    if a.size * 4 <= DUMP_LIMIT_BYTES:
+        files["disparity"] = a.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(seed).integers(0, a.size, DUMP_SAMPLE))
+        files["disparity_first_frame"] = a[0].astype(np.float32)
+        files["disparity_last_frame"] = a[-1].astype(np.float32)
+        files["disparity_sample"] = a.reshape(-1)[idx].astype(np.float32)
+    assert sum(v.nbytes for v in files.values()) <= DUMP_LIMIT_BYTES
+    for name, v in files.items():
+        np.save(os.path.join(dirpath, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in files.items()}
 
 
 def hbm_copy_gbps(device, nbytes=2 << 30, reps=5):
@@ -319,13 +364,18 @@ def run_c5(args, n_gpus, pkg, torch, device):
                        "peak": HBM_PEAK_GBS * n_gpus, "unit": "GB/s",
                        "frac": round(b_alg / (ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * n_gpus), 4),
                        "basis": "SURVEY 8d B_alg of one C5 frame over the frame time, against N x 8 TB/s"}
+    if args.dump_outputs:
+        res["dumped_outputs"] = dump_outputs(args.dump_outputs, out)
     if n_gpus == 1:
-        eng.set_profiling(True)
-        eng.match_device(dl.data_ptr(), dr.data_ptr(), W, H, W, out.data_ptr(), W, stream)
-        tstream.synchronize()
-        res["stages"] = {n: round(t, 4) for n, t, _ in eng.stage_times()}
-        eng.set_profiling(False)
+        if args.full:                    # per-stage split: a profiled frame of its own
+            eng.set_profiling(True)
+            eng.match_device(dl.data_ptr(), dr.data_ptr(), W, H, W, out.data_ptr(), W, stream)
+            tstream.synchronize()
+            res["stages"] = {n: round(t, 4) for n, t, _ in eng.stage_times()}
+            eng.set_profiling(False)
         res["disagreement_vs_full_frame"] = 0.0
+    elif not args.full:                  # the comparison needs a full frame on one device
+        res["disagreement_vs_full_frame"] = None
     else:
         tiled = out.cpu().numpy()
         eng.match_device(dl.data_ptr(), dr.data_ptr(), W, H, W, out.data_ptr(), W, stream)
@@ -337,11 +387,11 @@ def run_c5(args, n_gpus, pkg, torch, device):
 
 
 def c5_leg(args, world):
-    """The default run's `c5` block: bench.py --config c5 in a child process (own HIP context,
-    a fault there cannot take the C3 line with it), over the same number of GPUs."""
+    """The `--full` run's `c5` block: bench.py --config c5 --full in a child process (own HIP
+    context, a fault there cannot take the C3 line with it), over the same number of GPUs."""
     env = {k: v for k, v in os.environ.items() if k not in RANK_ENV}
     cmd = [sys.executable, os.path.abspath(__file__), "--config", "c5", "--gpus", str(world), "--steps",
-           str(args.c5_frames), "--warmup", "1", "--no-cpu-baseline", "--c5-only"]
+           str(args.c5_frames), "--warmup", "1", "--full", "--no-cpu-baseline", "--c5-only"]
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.c5_timeout)
     except subprocess.TimeoutExpired:
@@ -437,6 +487,11 @@ def main():
     ap.add_argument("--frames", type=int, default=64, help="frames per rank per step (BASELINE C4: batch 64)")
     ap.add_argument("--distinct", type=int, default=4, help="distinct synthetic pairs per rank")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: device copy rate, single-frame latency, "
+                         "the c5 block and (N = 1) the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's disparity maps (rank 0) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="one sgm_match_device call per frame")
     ap.add_argument("--rectify", action="store_true",
@@ -445,8 +500,8 @@ def main():
                     help="host buffers in and out (sgm_match_batch: pinned rings, H2D/D2H overlapped with the "
                          "kernels); PCIe-inclusive, reported beside the device-resident value, never as it")
     ap.add_argument("--dry-run", action="store_true", help="rank logic only: gloo, no HIP (CPU tests)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the default run's C5 block")
-    ap.add_argument("--c5-frames", type=int, default=10, help="timed C5 frames of the default run's c5 block")
+    ap.add_argument("--no-c5", action="store_true", help="skip the --full run's C5 block")
+    ap.add_argument("--c5-frames", type=int, default=10, help="timed C5 frames of the --full run's c5 block")
     ap.add_argument("--c5-timeout", type=int, default=300)
     ap.add_argument("--c5-only", action="store_true", help=argparse.SUPPRESS)
     # test-only: every rank on device 0 over gloo (RCCL cannot put two ranks on one GPU), so the
@@ -455,6 +510,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a torchrun environment: start the N ranks here, before any GPU call
     # (C5 is one process driving every device, so it needs no rank processes)
@@ -595,10 +652,15 @@ def main():
     elapsed_max = max_over_ranks(elapsed, None if args.share_device else device)
     shard = gather_shard(ids, elapsed, distributed, device=device_identity(device), group=wait_group)
 
-    # single-frame latency beside the batch throughput (BASELINE's C2 is quoted as a single
+    # what the last timed step left in the output buffers, before any other leg writes to them
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, host_o if args.host_io else out)
+
+    # --full: single-frame latency beside the batch throughput (BASELINE's C2 is quoted as a single
     # frame): one sgm_match_device per frame on resident buffers, HIP events on the stream
     single = None
-    if rank == 0 and not args.host_io:
+    if rank == 0 and args.full and not args.host_io:
         reps = 10
         one = lambda i: eng.match_device(ptr_l[i % len(ptr_l)], ptr_r[i % len(ptr_r)], W, H, W, ptr_o[i % len(ptr_o)],
                                          W, stream)
@@ -649,7 +711,7 @@ def main():
                 traffic_profile = {"hbm_bytes_per_launch": pmc["kernels"][dom[0]].get("hbm_bytes_per_launch"),
                                    "source": f"profiles/latest_pmc_{args.config}.json (rocprofv3 --pmc, separate run; "
                                              "tools/refresh_profiles.sh)", "git": pmc.get("git")}
-            copy_gbps = hbm_copy_gbps(device)
+            copy_gbps = hbm_copy_gbps(device) if args.full else None    # a 2 GiB copy run of its own
             roofline = {"bound": "hbm", "kernel": dom[0], "achieved": round(dom_achieved, 1),
                         "measured_copy_GBps": copy_gbps,
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(dom_achieved / HBM_PEAK_GBS, 4),
@@ -688,11 +750,13 @@ def main():
             "shard": shard,
             "distinct_devices": distinct_devices(shard),
         }
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
     eng.close()
     if rank == 0:
-        if args.config == "c3" and not args.no_c5 and not args.host_io and not args.rectify:
+        if args.full and args.config == "c3" and not args.no_c5 and not args.host_io and not args.rectify:
             res["c5"] = c5_leg(args, world)          # the other ranks wait at the barrier below
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(res))
     if distributed:

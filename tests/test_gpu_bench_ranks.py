@@ -23,7 +23,7 @@ def test_bench_two_ranks_on_one_device(config):
     env = {k: v for k, v in os.environ.items() if k not in RANK_VARS}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", config,
                         "--steps", "3", "--warmup", "1", "--frames", "4", "--distinct", "2", "--share-device",
-                        "--no-c5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=360,
+                        "--full", "--no-c5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=360,
                        cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -342,15 +342,15 @@ def test_tiled_device_equals_host_tiles(engine, oracle, synth, pkg, bands, halo,
 
 
 def test_bench_c5_block_on_one_device():
-    """bench.py --config c5 --gpus 1 (the driver's default run adds the same block): the full
-    frame on one device, with its roofline and stage split."""
+    """bench.py --config c5 --gpus 1 --full (the driver's --full run adds the same block): the
+    full frame on one device, with its roofline and stage split."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=300, cwd=root)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["c5"]["disagreement_vs_full_frame"] == 0.0

@@ -53,11 +53,11 @@ if [ "$MODE" = all ] || [ "$MODE" = tests ] || [ "$MODE" = final ]; then
   run gpu_tests 1200 $PYTEST --timeout 900 tests || exit 1
 fi
 if [ "$MODE" = final ]; then
-  run bench_final 600 python bench.py || exit 1
+  run bench_final 600 python bench.py --full || exit 1
   grep '^{' gpurun_out/bench_final.log > gpurun_out/bench_final.json
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  run bench 600 python bench.py --steps 5 --warmup 2
+  run bench 600 python bench.py --full --steps 5 --warmup 2
 fi
 if [ "$MODE" = ocv ]; then        # OpenCV modes: their GPU tests, per-stage lines, host calls
   run gpu_tests_ocv 900 $PYTEST --timeout 600 tests/test_gpu_ocv.py tests/test_gpu_ocv_compat.py \
@@ -68,7 +68,7 @@ fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
   rm -rf gpurun_out/prof
   run rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- \
-      python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline
+      python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline
   python3 tools/prof_compare.py gpurun_out/prof/run_kernel_trace.csv gpurun_out/rocprof.log > gpurun_out/prof_vs_bench.txt
 fi
 exit 0
