@@ -257,6 +257,10 @@ __device__ __forceinline__ uint32_t pk_shl(uint32_t a, int sh)
     return as_u(as_v2(a) << (u16x2_t){(unsigned short)sh, (unsigned short)sh});
 }
 __device__ __forceinline__ uint32_t pk_subs(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_sub_sat(as_v2(a), as_v2(b))); }
+// Pair group (sgm_device.h pair_group) of a line of LPL lanes holding DPL disparities per lane:
+// 8-lane lines (SGM_ROWS_LPL8) hold two groups of the launch's 16-lane DPL per lane
+__host__ __device__ constexpr int line_group(int dpl, int lpl) { return pair_group(lpl == 8 ? dpl / 2 : dpl); }
+
 // Relative state of a line from its absolute costs: Lr = Labs - min over the line's D
 // (LPL lanes per line: 16 = a whole 16-lane row, 8 = one parity of a row, see p16_rows)
 template <int DPL, int LPL = 16>
@@ -278,7 +282,9 @@ __device__ __forceinline__ void p16_relative(const uint32_t (&Labs)[DPL / 2], ui
 // One recurrence step of the lane's pairs, costs computed on the fly:
 //   L(d) = C(d) + min(Lr(d), Lr(d-1) + P1, Lr(d+1) + P1, P2),  C(d) = Hamming(cl, crk(d))
 // Lr: relative state (patterns) in/out. Labs: absolute L (patterns) out.
-// Per pair: q = Lr + P1 (1), neighbour align (1), minimum3 (1), min P2 (1), 4 xor + 4 bcnt
+// Pairs are interleaved (sgm_device.h pair_d): the neighbours of a pair are whole registers,
+// and a group of 16 disparities costs two v_alignbit at its ends, not one per pair.
+// Per pair: q = Lr + P1 (1), minimum3 (1), min P2 (1), 4 xor + 4 bcnt
 // + 1 shift-add for the two costs (the low cost rides on v_bcnt's accumulator), 1/2 for the
 // min reduction, 1 subtract.
 // LPL = 8: the line's lanes are every other lane of a 16-lane row, so the neighbouring lane
@@ -290,35 +296,39 @@ __device__ __forceinline__ void p16_step(uint32_t (&Lr)[DPL / 2], uint64_t cl, F
 {
     constexpr int M = DPL / 2;
     constexpr int SH = LPL == 8 ? 2 : 1;
+    constexpr int G = line_group(DPL, LPL), G2 = G / 2;   // pairs per group
     uint32_t q[M];
 #pragma unroll
     for (int i = 0; i < M; i++) q[i] = Lr[i] + P1P1;      // = pk_add: halves <= kInfP | kBaseP, no carry
-    // previous lane: its .hi is q(d0 - 1); next lane: its .lo is q(d0 + DPL)
+    // previous lane: its last .hi is q(d0 - 1); next lane: its first .lo is q(d0 + DPL)
     const uint32_t X = LPL == 32 ? line32_shr1(q[M - 1], kInfP2) : row_shr_n<SH>(q[M - 1], kInfP2);
     const uint32_t Y = LPL == 32 ? line32_shl1(q[0], kInfP2) : row_shl_n<SH>(q[0], kInfP2);
-    uint32_t Oprev = alignbit16(q[0], X);                 // (q(d-1), q(d)) for pair 0
 #pragma unroll
     for (int i = 0; i < M; i++) {
-        const uint32_t Onext = (i + 1 < M) ? alignbit16(q[i + 1], q[i]) : alignbit16(Y, q[M - 1]);
+        // pair i of a group holds (d_i, d_{i + G2}): both d-1 neighbours are pair i-1, both d+1
+        // neighbours pair i+1; only the group's end pairs take one half from outside it
+        const int i0 = i / G2 * G2, il = i - i0;          // the group's first pair, index inside it
+        const uint32_t Oprev = il > 0 ? q[i - 1] : alignbit16(q[i0 + G2 - 1], i0 > 0 ? q[i0 - 1] : X);
+        const uint32_t Onext = il + 1 < G2 ? q[i + 1] : alignbit16(i0 + G2 < M ? q[i0 + G2] : Y, q[i0]);
         const uint32_t t = pk_min(pk_min3_p(Oprev, Onext, Lr[i]), P2P2);
-        const uint32_t c1 = ham_acc(cl, crk(2 * i + 1), 0u);
-        uint32_t L = ham_acc(cl, crk(2 * i), t) + (c1 << 16);
+        const uint32_t c1 = ham_acc(cl, crk(pair_d(G, i, 1)), 0u);
+        uint32_t L = ham_acc(cl, crk(pair_d(G, i, 0)), t) + (c1 << 16);
         if (!EXACT) L = pk_max(L, imask[i]);
         Labs[i] = L;
-        Oprev = Onext;
     }
     p16_relative<DPL, LPL>(Labs, Lr);
 }
 
 // imask: kInfP in the halves with d >= D (0 elsewhere); start: the relative state of a
 // path's first pixel (L = C): kBase, or kInfP | kBase for d >= D.
-template <int DPL, bool EXACT>
+template <int DPL, bool EXACT, int LPL = 16>
 __device__ __forceinline__ void make_imask(int p, int D, uint32_t (&imask)[DPL / 2], uint32_t (&start)[DPL / 2])
 {
+    constexpr int G = line_group(DPL, LPL);
 #pragma unroll
     for (int i = 0; i < DPL / 2; i++) {
-        const int d = p * DPL + 2 * i;
-        imask[i] = EXACT ? 0u : ((d < D ? 0u : kInfP) | (d + 1 < D ? 0u : kInfP << 16));
+        const int dlo = p * DPL + pair_d(G, i, 0), dhi = p * DPL + pair_d(G, i, 1);
+        imask[i] = EXACT ? 0u : ((dlo < D ? 0u : kInfP) | (dhi < D ? 0u : kInfP << 16));
         start[i] = imask[i] | kBaseP2;
     }
 }
@@ -403,7 +413,7 @@ __device__ __forceinline__ void p16_horiz(const uint64_t* __restrict__ cL, const
     const uint64_t* cLr = cL + (size_t)yc * g.W;
     const uint64_t* cRr = cR + (size_t)yc * g.W;
     uint32_t imask[M], start[M];
-    make_imask<DPL, EXACT>(p, g.D, imask, start);
+    make_imask<DPL, EXACT, LPL>(p, g.D, imask, start);
     const uint32_t P1P1 = (uint32_t)g.P1 * 0x10001u, P2P2 = ((uint32_t)g.P2 + kBaseP) * 0x10001u;
     const int n = g.width1;
     const int xfirst = DX > 0 ? g.minX1 : g.maxX1 - 1;
@@ -593,7 +603,7 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     else { s0 = max(0, xb - g.maxX1 + 1); s1 = min(g.H, xb + NL - g.minX1); }
     if (s0 >= s1) return;                          // uniform over the workgroup
     uint32_t imask[M], start[M];
-    make_imask<DPL, EXACT>(p, g.D, imask, start);
+    make_imask<DPL, EXACT, LPL>(p, g.D, imask, start);
     const uint32_t P1P1 = (uint32_t)g.P1 * 0x10001u, P2P2 = ((uint32_t)g.P2 + kBaseP) * 0x10001u;
     uint32_t Lr[M];
 #pragma unroll
@@ -637,8 +647,12 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     uint32_t* srow = (uint32_t*)(lds + 2 * RS::BUF) + j * 32 * NWD;
     const float inv_u = 1.0f / (float)max(100 - g.uniq, 1);
     const uint32_t voff = (uint32_t)((min(max(xb + j, g.minX1), g.maxX1 - 1) - g.minX1) * g.D + (lane_act ? p * DPL : 0));
+    // The set's base in a scalar pair of its own: as a part of the 16-dword kernel-argument load it
+    // came from, the register allocator spilled and reloaded all 16 dwords around every step.
+    uint64_t vols0 = (uint64_t)uw.vols;
+    if constexpr (FUSE) asm volatile("" : "+s"(vols0));
     auto vload = [&](int s) {
-        const uint8_t* rb = uw.vols + (size_t)max(g.H - 1 - s, 0) * g.width1 * g.D;   // wave-uniform
+        const uint8_t* rb = (const uint8_t*)vols0 + (size_t)max(g.H - 1 - s, 0) * g.width1 * g.D;   // wave-uniform
 #pragma unroll
         for (int k = 0; k < 7; k++) wload_buf<DPL>(rb + (size_t)(k == 0 ? 0 : k + 1) * uw.vol_bytes, voff, vw[k]);
     };
@@ -646,6 +660,7 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
         wta_emask<DPL, EXACT>(p, g, emaskE, emaskO);
         vload(s0);
     }
+    const uint64_t* resrow = FUSE ? uw.res + (size_t)(g.H - 1 - s0) * g.W : nullptr;   // up+WTA: row y of step s0
     auto step = [&](int s, const uint64_t* bufc) {
         const int x = xb + j + rx * s;
         const bool valid = s < s1 && x >= g.minX1 && x < g.maxX1;
@@ -674,7 +689,7 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
         p16_step<DPL, EXACT, LPL>(Lr, cl, [&](int k) { return bufc[RS::phys(e_hi - k)]; }, P1P1, P2x, imask, Labs);
         if constexpr (FUSE) {
             __builtin_amdgcn_sched_barrier(0);
-            // + L_1: the low byte of each biased-f16 pattern (pair i holds d = 2i, 2i + 1)
+            // + L_1: the low byte of each biased-f16 pattern (pair i = bytes 2i, 2i + 1 of a cell)
 #pragma unroll
             for (int jj = 0; jj < NWD; jj++) {
                 const uint32_t a = Labs[2 * jj], b = 2 * jj + 1 < M ? Labs[2 * jj + 1] : 0u;
@@ -692,8 +707,9 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
             // descriptor's range, where the hardware drops them (no branch, and no trash slot:
             // 60 of 64 lanes storing into one shared 512-B slot every step made all the frames'
             // up+WTA waves contend on the same lines — 3 frames per launch ran 5x slower)
-            const __amdgpu_buffer_rsrc_t rr =
-                __builtin_amdgcn_make_buffer_rsrc((void*)(uw.res + (size_t)y * g.W), 0, g.W * 8, 0x00020000);
+            // (the row base is carried from step to step: one scalar subtract, no 64-bit multiply)
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)resrow, 0, g.W * 8, 0x00020000);
+            resrow -= g.W;
             typedef unsigned int v2u __attribute__((ext_vector_type(2)));
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), rr,
                                                   (valid && p == 0) ? (uint32_t)x * 8u : 0x80000000u, 0, 2);
@@ -795,8 +811,9 @@ template <int DPL>
 __host__ __device__ constexpr size_t wta_lds_bytes(int W) { return wta_key_bytes<DPL>(W) + RowLds::rest_bytes(W); }
 
 // WTA of the 4 pixels a wave holds (one per 16-lane row, lane p: d = p*DPL ..), from their
-// S in packed u16 pairs: E[j] = (S[4j], S[4j+2]), O[j] = (S[4j+1], S[4j+3]); halves past D or
-// past the lane's DPL hold 0xFFFF. srow: the row's LDS slice (16 lanes x 2 * NWD dwords).
+// S in packed u16 pairs by cell byte: E[j] = S of bytes (4j, 4j+2), O[j] of bytes (4j+1, 4j+3),
+// byte b holding d = p*DPL + vol_byte_d(b) (interleaved pairs); halves past D or past the
+// lane's DPL hold 0xFFFF. srow: the row's LDS slice (16 lanes x 2 * NWD dwords).
 template <int DPL, bool EXACT>
 __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], const uint32_t (&O)[(DPL + 3) / 4],
                                             int p, const Geom& g, float inv_u, uint32_t* srow)
@@ -806,11 +823,24 @@ __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], 
     constexpr int KB = DPL > 16 ? 5 : 4;
     constexpr uint32_t KMASK = (1u << KB) - 1;
     // ---- (minS, best): packed 16-bit keys S << KB | k, one 16-lane min over S*512 + d ----
+    // k of a half: the disparity its volume byte holds (interleaved pairs), so that equal S
+    // still order by true d. Real S <= 8 * 255, so S << KB stays inside its half and one 32-bit
+    // shift-or builds both keys; halves masked to 0xFFFF (k >= DPL, d >= D) would spill into
+    // the upper half, so those builds keep the per-half shift.
+    constexpr int G = pair_group(DPL);
+    auto kof = [](int b) { return (uint32_t)(b < DPL ? vol_byte_d(G, b) : b) & KMASK; };
     uint32_t km = 0xFFFFFFFFu;
 #pragma unroll
     for (int j = 0; j < NWD; j++) {
-        const uint32_t ke = pk_shl(E[j], KB) | (((uint32_t)(4 * j + 2) << 16) | (uint32_t)(4 * j));
-        const uint32_t ko = pk_shl(O[j], KB) | (((uint32_t)(4 * j + 3) << 16) | (uint32_t)(4 * j + 1));
+        uint32_t ce = (kof(4 * j + 2) << 16) | kof(4 * j), co = (kof(4 * j + 3) << 16) | kof(4 * j + 1);
+        uint32_t ke, ko;
+        if constexpr (EXACT && DPL >= 4) {
+            // v_lshl_or_b32 takes no literal: the constants stay in scalar registers, not in 2 * NWD
+            // more VGPRs
+            asm("" : "+s"(ce), "+s"(co));
+            ke = (E[j] << KB) | ce; ko = (O[j] << KB) | co;
+        }
+        else { ke = pk_shl(E[j], KB) | ce; ko = pk_shl(O[j], KB) | co; }
         km = pk_min(km, pk_min(ke, ko));
     }
     km = pk_min(km, alignbit16(km, km)) & 0xFFFFu;      // lane min key (low half)
@@ -822,7 +852,7 @@ __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], 
 #pragma unroll
     for (int j = 0; j < NWD; j++) { srow[p * 2 * NWD + j] = E[j]; srow[p * 2 * NWD + NWD + j] = O[j]; }
     auto s_at = [&](int d) {
-        const int kk = d % DPL;
+        const int kk = vol_d_byte(G, d % DPL);      // the byte of the lane's cell that holds d
         const uint32_t v = srow[(d / DPL) * 2 * NWD + (kk & 1) * NWD + (kk >> 2)];
         return (int)((v >> (16 * ((kk >> 1) & 1))) & 0xFFFFu);
     };
@@ -871,7 +901,8 @@ __device__ __forceinline__ void wta_emask(int p, const Geom& g, uint32_t (&emask
 {
 #pragma unroll
     for (int j = 0; j < (DPL + 3) / 4; j++) {
-        auto bad = [&](int k) { return k >= DPL || (!EXACT && p * DPL + k >= g.D); };
+        // b: byte of the lane's cell (interleaved pairs: it holds d = p * DPL + vol_byte_d)
+        auto bad = [&](int b) { return b >= DPL || (!EXACT && p * DPL + vol_byte_d(pair_group(DPL), b) >= g.D); };
         emaskE[j] = (bad(4 * j) ? 0xFFFFu : 0u) | (bad(4 * j + 2) ? 0xFFFF0000u : 0u);
         emaskO[j] = (bad(4 * j + 1) ? 0xFFFFu : 0u) | (bad(4 * j + 3) ? 0xFFFF0000u : 0u);
     }
@@ -1067,7 +1098,6 @@ void k_census_fused16(PathFrames pf, WtaFrames wf, CensusFrames cf, size_t vol_b
         if constexpr (DPL > 16) {           // D > 256: no up+WTA items (host layout)
             paths_block16<DPL, EXACT>(pf, vol_bytes, trash_off, g, pl, it, lds_dyn64);
         } else if ((it >> 24) == 8u) {      // up+WTA of frame f of wf
-            using RC = RowsCfg<DPL>;
             const int f = (int)((it >> 22) & 3u);
             if (f < wf.n) {
 #if SGM_UPWTA_PRIO
@@ -1119,6 +1149,8 @@ hipError_t launch_census(const uint8_t* L, const uint8_t* R, size_t stride, int 
 }
 
 static int dpl16_for(int D) { return D <= 32 ? 2 : D <= 64 ? 4 : D <= 128 ? 8 : D <= 256 ? 16 : 32; }
+// chunk size of the volumes' interleaved byte order for a search of D disparities (pair_group)
+int census_vol_group(int D) { return pair_group(dpl16_for(D)); }
 // lines per row-sweep workgroup (RowsCfg<DPL>::NL of the launch's DPL)
 static int rows_lines(int D)
 {

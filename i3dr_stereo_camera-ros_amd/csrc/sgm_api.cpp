@@ -26,6 +26,7 @@
 namespace sgm {
 hipError_t launch_census(const uint8_t*, const uint8_t*, size_t, int, int, uint64_t*, uint64_t*, hipStream_t);
 int census_path_items(const Geom&, unsigned, int, int, uint32_t*, int, int up_group = 0);
+int census_vol_group(int D);
 hipError_t launch_census_paths(const PathFrames&, size_t, const Geom&, const uint32_t*, int, hipStream_t,
                                const uint8_t* = nullptr, const uint8_t* = nullptr, size_t = 0);
 hipError_t launch_census_wta(const WtaFrames&, size_t, const Geom&, size_t, hipStream_t);
@@ -2217,6 +2218,13 @@ int sgm_debug_census_path(sgm_handle* h, const uint8_t* L, const uint8_t* R, int
     const size_t cells = (size_t)g.width1 * g.H * g.D;
     HIP_TRY(hipMemcpyAsync(vol, vols + (size_t)dir * l.vol_bytes, cells, hipMemcpyDeviceToHost, h->stream), "D2H");
     HIP_TRY(hipStreamSynchronize(h->stream), "sync");
+    // the device order is interleaved inside G-byte chunks (sgm_device.h pair_d): back to [D]
+    const int G = sgm::census_vol_group(g.D);
+    uint8_t t[16];
+    for (size_t c = 0; c + G <= cells; c += G) {
+        for (int b = 0; b < G; b++) t[sgm::vol_byte_d(G, b)] = vol[c + b];
+        memcpy(vol + c, t, G);
+    }
     return SGM_OK;
 }
 

@@ -96,6 +96,25 @@ __device__ __forceinline__ bool ocv_flagged(const Geom& g)
     return g.wide == 1 || (g.wide == 2 && *g.ovf != 0);
 }
 
+// Interleaved pair layout of the census path engine and its volumes. A lane's
+// DPL disparities are split into groups of G = min(DPL, 16); pair register i of a group holds
+// (d_i, d_{i + G/2}), so both d-1 neighbours of a pair are pair i-1 and both d+1 neighbours
+// pair i+1. Pairs are stored as bytes 2i, 2i+1: inside every G-byte chunk of a volume cell
+// byte b holds the chunk's disparity (b >> 1) + (G/2)(b & 1).
+// G is fixed by the launch's 16-lane DPL (D_pad / 16), whatever the lanes per line of a kernel.
+__host__ __device__ constexpr int pair_group(int dpl16) { return dpl16 < 16 ? dpl16 : 16; }
+// disparity index (inside the lane, or the cell) of half `hi` of pair register i
+__host__ __device__ constexpr int pair_d(int g, int i, int hi)
+{
+    return i / (g / 2) * g + i % (g / 2) + hi * (g / 2);
+}
+// disparity index held by byte b of a lane's (or a cell's) stored bytes, and its inverse
+__host__ __device__ constexpr int vol_byte_d(int g, int b) { return pair_d(g, b >> 1, b & 1); }
+__host__ __device__ constexpr int vol_d_byte(int g, int k)
+{
+    return k / g * g + 2 * (k % g % (g / 2)) + k % g / (g / 2);
+}
+
 // Direction r = (rx, ry): L_r(p) depends on L_r(p - r). Engine volume order.
 __host__ __device__ constexpr int dir_rx(int i) { return i == 2 || i == 4 || i == 6 ? 1 : (i == 3 || i == 5 || i == 7 ? -1 : 0); }
 __host__ __device__ constexpr int dir_ry(int i) { return i == 0 || i == 2 || i == 3 ? 1 : (i == 1 || i == 4 || i == 5 ? -1 : 0); }
