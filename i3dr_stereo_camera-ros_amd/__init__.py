@@ -24,16 +24,18 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsgm_hip.so")
 
-ABI_VERSION = 4     # include/sgm_hip.h SGM_ABI_VERSION
+ABI_VERSION = 5     # include/sgm_hip.h SGM_ABI_VERSION
 MODE_OCV_SGBM5 = 0
 MODE_OCV_HH8 = 1
 MODE_CENSUS8 = 2
+MODE_OCV_BM = 3     # cv::StereoBM, the node's default algorithm (restated, unverified against OpenCV)
 
 SGM_OK, SGM_ERR_ARG, SGM_ERR_PARAM, SGM_ERR_DEVICE, SGM_ERR_ALLOC, SGM_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 # reference enum (cfg/i3DR_Disparity.cfg:11-17) + the new entry this engine adds
 CV_StereoBM, CV_StereoSGBM, I3DR_StereoSGM, CV_StereoBMCuda, CV_StereoBPCuda, CV_StereoCSBPCuda = range(6)
 HIP_StereoSGM = 6
+HIP_StereoBM = 7     # the same engine in MODE_OCV_BM
 
 MISSING_Z = 10000.0  # image_geometry::StereoCameraModel::MISSING_Z
 
@@ -68,6 +70,8 @@ EXPORTS = [
     "sgm_stage_launches", "sgm_disparity_to_msg", "sgm_calc_q", "sgm_depth_points", "sgm_rectify_map",
     "sgm_remap_cubic", "sgm_cubic_table", "sgm_set_rectification", "sgm_match_device_batch_rect", "sgm_debug_census",
     "sgm_debug_census_path", "sgm_debug_ocv_cost", "sgm_debug_median3", "sgm_debug_speckle", "sgm_debug_path_items",
+    "sgm_default_bm_params", "sgm_set_bm_params", "sgm_get_bm_params", "sgm_check_bm_params", "sgm_debug_bm_prefilter",
+    "sgm_debug_bm_sad",
 ]
 
 
@@ -88,6 +92,20 @@ class SgmParams(ctypes.Structure):
         for k, v in kw.items():
             setattr(p, k, int(v))
         return p
+
+
+class BmParams(ctypes.Structure):
+    """`sgm_bm_params` of include/sgm_hip.h: the two cv::StereoBM values `sgm_params` has no field for."""
+    _fields_ = [("texture_threshold", ctypes.c_int), ("prefilter_size", ctypes.c_int)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def copy(self, **kw):
+        b = BmParams(self.texture_threshold, self.prefilter_size)
+        for k, v in kw.items():
+            setattr(b, k, int(v))
+        return b
 
 
 _lib = None
@@ -164,6 +182,13 @@ def load_library(path=None):
     L.sgm_debug_median3.argtypes = [vp, vp, ci, ci]
     L.sgm_debug_speckle.argtypes = [vp, vp, ci, ci, ci, ci, ci]
     L.sgm_debug_path_items.argtypes = [P(SgmParams), ci, ci, ctypes.c_uint, ci, ci, ci, vp, ci]
+    L.sgm_default_bm_params.argtypes = [P(BmParams)]
+    L.sgm_default_bm_params.restype = None
+    L.sgm_set_bm_params.argtypes = [vp, P(BmParams)]
+    L.sgm_get_bm_params.argtypes = [vp, P(BmParams)]
+    L.sgm_check_bm_params.argtypes = [P(SgmParams), P(BmParams), ci, ci]
+    L.sgm_debug_bm_prefilter.argtypes = [vp, vp, ci, ci, sz, vp]
+    L.sgm_debug_bm_sad.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
     _lib = L
     return L
 
@@ -174,6 +199,23 @@ def default_params(mode=MODE_CENSUS8, **kw):
     for k, v in kw.items():
         setattr(p, k, int(v))
     return p
+
+
+def default_bm_params(**kw):
+    b = BmParams()
+    load_library().sgm_default_bm_params(ctypes.byref(b))
+    for k, v in kw.items():
+        setattr(b, k, int(v))
+    return b
+
+
+def bm_geometry(params, width, height):
+    """(X0, X1, width1, D, invalid) of MODE_OCV_BM: columns [X0, X1) are computed, X0 = max(D - 1 +
+    minD, 0), X1 = min(W, W + minD); an empty range leaves the whole frame invalid."""
+    minD, D = params.min_disparity, params.num_disparities
+    x0, x1 = max(D - 1 + minD, 0), min(width, width + minD)
+    w1 = 0 if (x0 >= width or x1 <= 0 or x1 <= x0) else x1 - x0
+    return dict(X0=x0, X1=x1, width1=w1, D=D, invalid=(minD - 1) * 16)
 
 
 def device_count():
@@ -239,6 +281,15 @@ class Engine:
         p = SgmParams()
         self._check(self.lib.sgm_get_params(self.h, ctypes.byref(p)))
         return p
+
+    def set_bm_params(self, b):
+        """The BM-only parameters (texture threshold, pre-filter size) of MODE_OCV_BM matches."""
+        self._check(self.lib.sgm_set_bm_params(self.h, ctypes.byref(b)))
+
+    def get_bm_params(self):
+        b = BmParams()
+        self._check(self.lib.sgm_get_bm_params(self.h, ctypes.byref(b)))
+        return b
 
     def match(self, left, right):
         left = np.ascontiguousarray(left, np.uint8)
@@ -485,6 +536,27 @@ class Engine:
         self._check(self.lib.sgm_debug_ocv_cost(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(C)))
         return C
 
+    def bm_prefilter(self, img):
+        """MODE_OCV_BM: the XSOBEL pre-filtered image (u8)."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        out = np.empty((h, w), np.uint8)
+        self._check(self.lib.sgm_debug_bm_prefilter(self.h, _ptr(img), w, h, w, _ptr(out)))
+        return out
+
+    def bm_sad(self, left, right):
+        """MODE_OCV_BM, small frames: (SAD int32 [H][X1 - X0][D], texture int32 [H][X1 - X0]) of the
+        fused kernel. The last SAD index is e = D - 1 - (d - minD): e = 0 is the largest disparity.
+        Rows outside [w/2, H - w/2) are 0."""
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        h, w = left.shape
+        e = bm_geometry(self.get_params(), w, h)
+        sad = np.zeros((h, e["width1"], e["D"]), np.int32)
+        tex = np.zeros((h, e["width1"]), np.int32)
+        self._check(self.lib.sgm_debug_bm_sad(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(sad), _ptr(tex)))
+        return sad, tex
+
     def median3(self, disp):
         d = np.ascontiguousarray(disp, np.int16).copy()
         h, w = d.shape
@@ -584,8 +656,18 @@ def right_matcher_params(p):
     """cv::ximgproc::createRightMatcher for a StereoSGBM: minD' = -(minD + D) + 1, same D /
     block / P1 / P2 / mode / preFilterCap, uniqueness 0, disp12MaxDiff 1e6, no speckle filter
     (reference calls it at matcherOpenCVSGBM.cpp:48)."""
+    if p.mode == MODE_OCV_BM:
+        return p.copy(min_disparity=-(p.min_disparity + p.num_disparities) + 1, uniqueness_ratio=0,
+                      speckle_window_size=0, speckle_range=0)
     return p.copy(min_disparity=-(p.min_disparity + p.num_disparities) + 1, uniqueness_ratio=0,
                   disp12_max_diff=1000000, speckle_window_size=0)
+
+
+def right_matcher_bm_params(b):
+    """cv::ximgproc::createRightMatcher for a StereoBM (with right_matcher_params): minD' = -(minD + D)
+    + 1, same D / block / caps, texture threshold 0, uniqueness 0, no speckle filter. Restated, not
+    verified against ximgproc."""
+    return b.copy(texture_threshold=0)
 
 
 class MatcherHIPSGM:
@@ -617,6 +699,15 @@ class MatcherHIPSGM:
 
     # --- AbstractStereoMatcher ----------------------------------------------------------
     def init(self):
+        self.bm_params = default_bm_params()
+        if self.mode == MODE_OCV_BM:
+            # cv::StereoBM::create(64, 9) starting point (matcherOpenCVBlock.cpp): minDisparity 0,
+            # 64 disparities, block 9, preFilterCap 31 / size 9, texture 10, uniqueness 15, no speckles
+            self.params = default_params(self.mode, min_disparity=0, num_disparities=64, block_size=9,
+                                         prefilter_cap=31, uniqueness_ratio=15, speckle_window_size=0,
+                                         speckle_range=0, disp12_max_diff=-1)
+            self._engine = None
+            return
         # cv::StereoSGBM::create(64, 9, 5) equivalent starting point (matcherOpenCVSGBM.cpp:14)
         p = default_params(self.mode)
         p.ocv_compat = ocv_compat_from_env(p.ocv_compat)
@@ -676,11 +767,13 @@ class MatcherHIPSGM:
     def setP2(self, p2):
         self.params.p2 = int(p2)
 
-    def setTextureThreshold(self, threshold):              # not used by SGBM
-        pass
+    def setTextureThreshold(self, threshold):              # BM mode only; not used by SGBM
+        if self.mode == MODE_OCV_BM:
+            self.bm_params.texture_threshold = int(threshold)
 
-    def setPreFilterSize(self, size):                      # not used by SGBM
-        pass
+    def setPreFilterSize(self, size):                      # BM mode only; not used by SGBM
+        if self.mode == MODE_OCV_BM:
+            self.bm_params.prefilter_size = int(size)
 
     def setOcclusionDetection(self, enable):               # not used by SGBM
         pass
@@ -690,9 +783,11 @@ class MatcherHIPSGM:
             self._engine = Engine(self.device)
         return self._engine
 
-    def _run(self, params, a, b, f32=False):
+    def _run(self, params, a, b, f32=False, bm=None):
         eng = self._engine_for()
         eng.set_params(params)
+        if params.mode == MODE_OCV_BM:
+            eng.set_bm_params(bm if bm is not None else self.bm_params)
         return eng.match_f32(a, b) if f32 else eng.match(a, b)
 
     def forwardMatch(self):
@@ -706,11 +801,14 @@ class MatcherHIPSGM:
                 self.disparity_lr = self._run(self.params, self.left, self.right, f32=True)
             return 0
         except Exception as e:  # mirrors the catch(cv::Exception&) -> -1
-            sys.stderr.write("Error in HIP SGM parameters\n%s\n" % e)
+            # matcherOpenCVSGBM.cpp:40 / matcherOpenCVBlock.cpp:40 style
+            what = "HIP StereoBM" if self.mode == MODE_OCV_BM else "HIP SGM"
+            sys.stderr.write("Error in %s parameters\n%s\n" % (what, e))
             return -1
 
     def backwardMatch(self):
-        self.disparity_rl = self._run(right_matcher_params(self.params), self.right, self.left)
+        self.disparity_rl = self._run(right_matcher_params(self.params), self.right, self.left,
+                                      bm=right_matcher_bm_params(self.bm_params))
         return 0
 
     def match(self):
@@ -768,7 +866,7 @@ def parameter_callback(config, state):
         return config
     config["prefilter_size"] |= 1
     if config["stereo_algorithm"] in (CV_StereoBM, CV_StereoSGBM, CV_StereoBMCuda, CV_StereoBPCuda,
-                                      CV_StereoCSBPCuda, HIP_StereoSGM):
+                                      CV_StereoCSBPCuda, HIP_StereoSGM, HIP_StereoBM):
         config["correlation_window_size"] |= 1
         config["disparity_range"] = (config["disparity_range"] // 16) * 16
     if config["stereo_algorithm"] == I3DR_StereoSGM and config["correlation_window_size"] > 17:

@@ -56,6 +56,10 @@ hipError_t launch_ocv_vwta(const int16_t*, const int16_t*, const void*, size_t, 
 int ocv_vwta_dir(int ndir);
 hipError_t launch_ocv_wta(const int16_t*, const void*, size_t, int, const Geom&, int16_t*, size_t, hipStream_t);
 int ocv_evol_mode(const Geom&, int, int);
+hipError_t launch_bm_prefilter(const uint8_t*, const uint8_t*, size_t, int, int, int, uint8_t*, uint8_t*, hipStream_t);
+BmPlan bm_plan(const Geom&, int);
+hipError_t launch_bm_match(const uint8_t*, const uint8_t*, const Geom&, const BmPlan&, int16_t*, size_t, void*, int*,
+                           int*, hipStream_t);
 }  // namespace sgm
 
 using sgm::Geom;
@@ -75,11 +79,54 @@ constexpr size_t kTrashBytes = 4096;   // >= 64 lanes x 32 disparities (census_s
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // effective parameters — identical rules to the oracle (oracle/sgm_oracle.c effective())
-int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err)
+// cv::filterSpeckles' maxDiff per unit of sgm_params.speckle_range: StereoSGBM passes
+// 16 * speckleRange (its disparities are x16), StereoBM passes speckleRange unscaled.
+constexpr int kSpeckleScaleSgbm = 16;
+constexpr int kSpeckleScaleBm = 1;
+int speckle_scale(int mode) { return mode == SGM_MODE_OCV_BM ? kSpeckleScaleBm : kSpeckleScaleSgbm; }
+
+constexpr sgm_bm_params kBmDefaults = {10, 9};   // texture_threshold, prefilter_size
+
+// SGM_MODE_OCV_BM: nothing is repaired (the validation step of the BM specification).
+int make_geom_bm(const sgm_params& p, const sgm_bm_params& bm, int W, int H, Geom& g, std::string& err)
+{
+    if (bm.prefilter_size < 5 || bm.prefilter_size > 255 || bm.prefilter_size % 2 == 0) {
+        err = "StereoBM: preFilterSize must be odd and within 5..255";
+        return SGM_ERR_PARAM;
+    }
+    if (p.prefilter_cap < 1 || p.prefilter_cap > 63) { err = "StereoBM: preFilterCap must be within 1..63"; return SGM_ERR_PARAM; }
+    const int w = p.block_size;
+    if (w < 5 || w > 255 || w % 2 == 0 || w >= std::min(W, H)) {
+        err = "StereoBM: SADWindowSize must be odd, within 5..255 and smaller than the image";
+        return SGM_ERR_PARAM;
+    }
+    if (bm.texture_threshold < 0) { err = "StereoBM: texture threshold must be non-negative"; return SGM_ERR_PARAM; }
+    if (p.uniqueness_ratio < 0) { err = "StereoBM: uniqueness ratio must be non-negative"; return SGM_ERR_PARAM; }
+    if (p.disp12_max_diff >= 0) {
+        err = "StereoBM: disp12MaxDiff >= 0 (validateDisparity) is not implemented; -1 switches it off";
+        return SGM_ERR_UNSUPPORTED;
+    }
+    g = Geom{};
+    g.W = W; g.H = H;
+    g.minD = p.min_disparity; g.D = p.num_disparities;
+    g.SW2 = g.SH2 = w / 2;
+    g.ftzero = p.prefilter_cap;
+    g.uniq = p.uniqueness_ratio;
+    g.bm_tex = bm.texture_threshold;
+    g.subpix = 1;
+    g.invalid = (g.minD - 1) * 16;
+    // column range [X0, X1): s = D - 1 + minD, X0 = max(s, 0), X1 = min(W, W + minD)
+    g.minX1 = std::max(g.D - 1 + g.minD, 0);
+    g.maxX1 = std::min(W, W + g.minD);
+    g.width1 = (g.minX1 >= W || g.maxX1 <= 0 || g.maxX1 <= g.minX1) ? 0 : g.maxX1 - g.minX1;
+    return SGM_OK;
+}
+
+int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err, const sgm_bm_params* bm = nullptr)
 {
     if (W <= 0 || H <= 0) { err = "image size must be positive"; return SGM_ERR_ARG; }
     if (W > 32767 || H > 32767) { err = "image larger than 32767 pixels"; return SGM_ERR_UNSUPPORTED; }
-    if (p.mode < SGM_MODE_OCV_SGBM5 || p.mode > SGM_MODE_CENSUS8) { err = "unknown mode"; return SGM_ERR_PARAM; }
+    if (p.mode < SGM_MODE_OCV_SGBM5 || p.mode > SGM_MODE_OCV_BM) { err = "unknown mode"; return SGM_ERR_PARAM; }
     if (p.num_disparities <= 0 || p.num_disparities % 16 != 0) {
         err = "numDisparities must be a positive multiple of 16 (OpenCV: CV_Assert(D % 16 == 0))";
         return SGM_ERR_PARAM;
@@ -92,6 +139,7 @@ int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err)
                                          : "numDisparities > 2048 is not supported";
         return SGM_ERR_UNSUPPORTED;
     }
+    if (p.mode == SGM_MODE_OCV_BM) return make_geom_bm(p, bm ? *bm : kBmDefaults, W, H, g, err);
     g = Geom{};
     g.W = W; g.H = H;
     g.minD = p.min_disparity; g.D = p.num_disparities;
@@ -141,7 +189,17 @@ int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err)
     return SGM_OK;
 }
 
-bool use_median(const sgm_params& p) { return p.mode != SGM_MODE_CENSUS8 || p.median != 0; }
+bool use_median(const sgm_params& p)
+{
+    if (p.mode == SGM_MODE_OCV_BM) return false;   // cv::StereoBM has no median
+    return p.mode != SGM_MODE_CENSUS8 || p.median != 0;
+}
+
+// the speckle filter of a frame: BM also needs speckle_range >= 0 (OpenCV's condition)
+bool use_speckle(const sgm_params& p)
+{
+    return p.speckle_window_size > 0 && (p.mode != SGM_MODE_OCV_BM || p.speckle_range >= 0);
+}
 
 struct Workspace {
     void* base = nullptr;
@@ -153,6 +211,7 @@ struct Workspace {
 struct sgm_handle {
     int device = 0;
     sgm_params params{};
+    sgm_bm_params bm = kBmDefaults;   // SGM_MODE_OCV_BM only
     hipStream_t stream = nullptr;
     std::string err;
     std::mutex mu;
@@ -333,6 +392,8 @@ struct Layout {
     size_t items[2] = {}; int n_items[2] = {};             // path work lists: one frame / a group
     size_t planes = 0, bufA = 0, bufB = 0, ovols = 0, ovf = 0;  // ocv
     size_t ores = 0;                                       // ocv: per-pixel results of k_ocv_vwta
+    size_t bmL = 0, bmR = 0, bmV = 0;                      // bm: pre-filtered images, HBM column sums
+    sgm::BmPlan bm{};                                      // bm: tiling of the fused kernel
     size_t tmp = 0, lab = 0, cnt = 0;                      // post
     size_t inL = 0, inR = 0, out = 0, outf = 0;            // host-API staging (int16 / float out)
     size_t total = 0;
@@ -347,7 +408,7 @@ bool use_up_wta()
     return !e || std::atoi(e) != 0;
 }
 
-Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0)
+Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0, int n_cu = 0)
 {
     Layout l;
     size_t off = 0;
@@ -355,7 +416,12 @@ Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group =
     auto take_codes = [&](size_t n) { return take((n + 2 * sgm::kCodeMargin) * 8) + 8 * sgm::kCodeMargin; };
     const size_t WH = (size_t)g.W * g.H;
     const size_t cells = (size_t)std::max(g.width1, 0) * g.H * g.D;
-    if (p.mode == SGM_MODE_CENSUS8) {
+    if (p.mode == SGM_MODE_OCV_BM) {
+        l.bmL = take(WH);
+        l.bmR = take(WH);
+        l.bm = sgm::bm_plan(g, n_cu);
+        l.bmV = take(l.bm.vbytes);
+    } else if (p.mode == SGM_MODE_CENSUS8) {
         l.vol_bytes = align_up(cells + kTrashBytes);   // + trash slot for masked stores
 #if SGM_VOL_PAD_BYTES > 0
         // extra bytes per volume slot (a measurement build: tools/build_variant.sh, -DSGM_VOL_PAD_BYTES=N)
@@ -464,7 +530,7 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
     char* ws = (char*)h->ws.base;
     const double WH = (double)g.W * g.H;
     const int16_t* raw = (const int16_t*)(ws + l.tmp) + tmp_off;
-    const bool med = use_median(p), spk = p.speckle_window_size > 0;
+    const bool med = use_median(p), spk = use_speckle(p);
     if (med && !spk) {
         rec.begin("median3", 4 * WH);
         HIP_TRY(sgm::launch_median3(raw, g.W, dOut, out_stride, g.W, g.H, h->stream), "median3");
@@ -472,7 +538,7 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
     if (spk) {   // with a median, the speckle tiles apply it first (one launch less)
         rec.begin(med ? "median3+speckle" : "speckle", (med ? 4 : 0) * WH + 14 * WH);
         HIP_TRY(sgm::launch_speckle(med ? raw : nullptr, g.W, dOut, out_stride, g.W, g.H, g.invalid,
-                                    p.speckle_window_size, 16 * p.speckle_range, (int*)(ws + l.lab),
+                                    p.speckle_window_size, speckle_scale(p.mode) * p.speckle_range, (int*)(ws + l.lab),
                                     (int*)(ws + l.cnt), h->stream),
                 "speckle");
     }
@@ -523,6 +589,15 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
     if (g.width1 <= 0) {
         rec.begin("fill_invalid", 2 * WH);
         HIP_TRY(sgm::launch_fill16(dst, dst_stride, g.W, g.H, g.invalid, st), "fill");
+    } else if (p.mode == SGM_MODE_OCV_BM) {
+        // pre-filter of both images, then the fused SAD + WTA kernel (no volume in HBM: it reads
+        // the two pre-filtered images, L2-resident, and writes the disparity)
+        uint8_t* PL = (uint8_t*)(ws + l.bmL);
+        uint8_t* PR = (uint8_t*)(ws + l.bmR);
+        rec.begin("bm_prefilter", 4 * WH);
+        HIP_TRY(sgm::launch_bm_prefilter(dL, dR, stride, g.W, g.H, g.ftzero, PL, PR, st), "bm_prefilter");
+        rec.begin("bm_match", 2 * WH + 2 * WH + 2 * (double)g.width1 * (g.H - 2 * g.SW2));
+        HIP_TRY(sgm::launch_bm_match(PL, PR, g, l.bm, dst, dst_stride, ws + l.bmV, nullptr, nullptr, st), "bm_match");
     } else if (p.mode == SGM_MODE_CENSUS8) {
         uint64_t* cL = (uint64_t*)(ws + l.cL[0]);
         uint64_t* cR = (uint64_t*)(ws + l.cR[0]);
@@ -769,10 +844,10 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
 
 int prepare(sgm_handle* h, int W, int H, bool host_io, Geom& g, Layout& l, int group = 0)
 {
-    int rc = make_geom(h->params, W, H, g, h->err);
+    int rc = make_geom(h->params, W, H, g, h->err, &h->bm);
     if (rc) return rc;
     if ((rc = ensure_stream(h))) return rc;
-    l = make_layout(h->params, g, host_io, group);
+    l = make_layout(h->params, g, host_io, group, h->n_cu);
     // the uploaded path work list lives in the workspace: any other use of it invalidates it
     if (h->params.mode != SGM_MODE_CENSUS8) { h->items_key[0].clear(); h->items_key[1].clear(); }
     return ensure_ws(h, l.total);
@@ -811,6 +886,7 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
         if (extra + reserve > free_b) break;
         if (!q && sgm_create(&q, h->device) != SGM_OK) break;
         q->params = h->params;
+        q->bm = h->bm;
         Geom gq;
         Layout lq;
         if (prepare(q, W, H, false, gq, lq) != SGM_OK) {   // e.g. an allocation failure: fewer lanes
@@ -892,7 +968,7 @@ int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, 
     // f32 output that is the WTA's own (census, no median / speckles) into a registered, mapped
     // host buffer: the WTA writes the float rows there itself (no to-float pass, no copy back)
     float* outf = nullptr;
-    if (f32 && census && !use_median(p) && p.speckle_window_size <= 0) {
+    if (f32 && census && !use_median(p) && !use_speckle(p)) {
         const size_t need = out_stride * 4 * (size_t)(H - 1) + (size_t)W * 4;
         for (const auto& r : h->regs)
             if (r.dev && (char*)out >= r.host && (char*)out + need <= r.host + r.bytes) {
@@ -955,7 +1031,38 @@ void sgm_default_params(sgm_params* p, int mode)
         p->uniqueness_ratio = 15; p->disp12_max_diff = 0; p->prefilter_cap = 31; p->speckle_window_size = 100;
         p->speckle_range = 4; p->subpixel = 1; p->lr_check = 1; p->median = 1;
         p->ocv_compat = SGM_OCV_COMPAT_MELODIC;   // the reference's Dockerfile:1 (melodic, OpenCV 3.2 SSE2)
+        if (mode == SGM_MODE_OCV_BM) {            // cv::StereoBM: disp12MaxDiff -1 = off, nothing SGBM-only
+            p->disp12_max_diff = -1; p->p1 = p->p2 = 0; p->median = 0; p->lr_check = 0; p->ocv_compat = 0;
+        }
     }
+}
+
+void sgm_default_bm_params(sgm_bm_params* p)
+{
+    if (p) *p = kBmDefaults;
+}
+
+int sgm_set_bm_params(sgm_handle* h, const sgm_bm_params* p)
+{
+    if (!h || !p) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->bm = *p;
+    return SGM_OK;
+}
+
+int sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p)
+{
+    if (!h || !p) return SGM_ERR_ARG;
+    *p = h->bm;
+    return SGM_OK;
+}
+
+int sgm_check_bm_params(const sgm_params* p, const sgm_bm_params* bm, int width, int height)
+{
+    if (!p || !bm) return SGM_ERR_ARG;
+    Geom g;
+    std::string err;
+    return make_geom(*p, width, height, g, err, bm);
 }
 
 int sgm_create(sgm_handle** out, int device)
@@ -1112,7 +1219,7 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
         return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification runs in the census mode (use sgm_remap_cubic)");
     Geom g;
     Layout l;
-    int rc = make_geom(h->params, W, H, g, h->err);
+    int rc = make_geom(h->params, W, H, g, h->err, &h->bm);
     if (rc) return rc;
     if (h->rect_on && g.width1 <= 0)
         return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
@@ -1312,6 +1419,7 @@ static int open_subs(sgm_handle* h, const int* devices, int n_dev, std::vector<i
             if (rc) return fail(h, rc, "cannot open device " + std::to_string(devs[i]));
         }
         h->sub[i]->params = h->params;
+        h->sub[i]->bm = h->bm;
     }
     return SGM_OK;
 }
@@ -1555,7 +1663,7 @@ int stream_host_frames(sgm_handle* h, const uint8_t* const* lefts, const uint8_t
     if (n == 0) return SGM_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     Geom g;
-    int rc = make_geom(h->params, W, H, g, h->err);
+    int rc = make_geom(h->params, W, H, g, h->err, &h->bm);
     if (rc) return rc;
     const bool pipelined = h->params.mode == SGM_MODE_CENSUS8 && n >= 2 && g.width1 > 0;
     Layout l;
@@ -2232,7 +2340,8 @@ int sgm_debug_ocv_cost(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W,
 {
     if (!h || !L || !R || !cost) return SGM_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->params.mode == SGM_MODE_CENSUS8) return fail(h, SGM_ERR_PARAM, "OCV mode required");
+    if (h->params.mode == SGM_MODE_CENSUS8 || h->params.mode == SGM_MODE_OCV_BM)
+        return fail(h, SGM_ERR_PARAM, "OCV mode required");
     Geom g;
     Layout l;
     int rc = prepare(h, W, H, true, g, l);
@@ -2260,6 +2369,60 @@ int sgm_debug_ocv_cost(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W,
     HIP_TRY(hipMemcpyAsync(cost, A, cells * 2, hipMemcpyDeviceToHost, h->stream), "D2H");
     HIP_TRY(hipStreamSynchronize(h->stream), "sync");
     return SGM_OK;
+}
+
+int sgm_debug_bm_prefilter(sgm_handle* h, const uint8_t* img, int W, int H, size_t stride, uint8_t* out)
+{
+    if (!h || !img || !out || stride < (size_t)std::max(W, 0)) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->params.mode != SGM_MODE_OCV_BM) return fail(h, SGM_ERR_PARAM, "BM mode required");
+    Geom g;
+    Layout l;
+    int rc = prepare(h, W, H, true, g, l);
+    if (rc || (rc = order_after_last(h, h->stream))) return rc;
+    char* ws = (char*)h->ws.base;
+    HIP_TRY(hipMemcpy2DAsync(ws + l.inL, W, img, stride, W, H, hipMemcpyHostToDevice, h->stream), "H2D");
+    HIP_TRY(sgm::launch_bm_prefilter((const uint8_t*)(ws + l.inL), nullptr, W, W, H, g.ftzero, (uint8_t*)(ws + l.bmL),
+                                     nullptr, h->stream),
+            "bm_prefilter");
+    HIP_TRY(hipMemcpyAsync(out, ws + l.bmL, (size_t)W * H, hipMemcpyDeviceToHost, h->stream), "D2H");
+    HIP_TRY(hipStreamSynchronize(h->stream), "sync");
+    return SGM_OK;
+}
+
+int sgm_debug_bm_sad(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, size_t stride, int32_t* sad,
+                     int32_t* texture)
+{
+    if (!h || !L || !R || stride < (size_t)std::max(W, 0)) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->params.mode != SGM_MODE_OCV_BM) return fail(h, SGM_ERR_PARAM, "BM mode required");
+    Geom g;
+    Layout l;
+    int rc = prepare(h, W, H, true, g, l);
+    if (rc || (rc = order_after_last(h, h->stream))) return rc;
+    if (g.width1 <= 0) return SGM_OK;
+    const size_t pix = (size_t)g.width1 * H, cells = pix * g.D;
+    if (cells > ((size_t)1 << 27)) return fail(h, SGM_ERR_UNSUPPORTED, "sgm_debug_bm_sad is for small frames");
+    // the debug planes sit behind the match workspace
+    const size_t vol_off = align_up(l.total), tex_off = vol_off + align_up(cells * 4);
+    if ((rc = ensure_ws(h, tex_off + align_up(pix * 4)))) return rc;
+    char* ws = (char*)h->ws.base;
+    hipStream_t st = h->stream;
+    HIP_TRY(hipMemcpy2DAsync(ws + l.inL, W, L, stride, W, H, hipMemcpyHostToDevice, st), "H2D");
+    HIP_TRY(hipMemcpy2DAsync(ws + l.inR, W, R, stride, W, H, hipMemcpyHostToDevice, st), "H2D");
+    HIP_TRY(hipMemsetAsync(ws + vol_off, 0, tex_off + align_up(pix * 4) - vol_off, st), "hipMemsetAsync");
+    uint8_t* PL = (uint8_t*)(ws + l.bmL);
+    uint8_t* PR = (uint8_t*)(ws + l.bmR);
+    HIP_TRY(sgm::launch_bm_prefilter((const uint8_t*)(ws + l.inL), (const uint8_t*)(ws + l.inR), W, W, H, g.ftzero, PL,
+                                     PR, st),
+            "bm_prefilter");
+    HIP_TRY(sgm::launch_bm_match(PL, PR, g, l.bm, (int16_t*)(ws + l.out), W, ws + l.bmV, (int*)(ws + vol_off),
+                                 (int*)(ws + tex_off), st),
+            "bm_match");
+    if (sad) HIP_TRY(hipMemcpyAsync(sad, ws + vol_off, cells * 4, hipMemcpyDeviceToHost, st), "D2H");
+    if (texture) HIP_TRY(hipMemcpyAsync(texture, ws + tex_off, pix * 4, hipMemcpyDeviceToHost, st), "D2H");
+    HIP_TRY(hipStreamSynchronize(st), "sync");
+    return mark_done(h, st);
 }
 
 static int debug_post(sgm_handle* h, int16_t* disp, int W, int H, int which, int nv, int ms, int md)

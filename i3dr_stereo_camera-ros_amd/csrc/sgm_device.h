@@ -51,6 +51,19 @@ struct Geom {
                             // 32767 - P2 under SIMD_SAT: (short)(minLr + P2) must not wrap)
     int evol;               // OCV: the plain kernels' path volumes hold deficit planes (C' - L in
                             // 9 bits: ocv_evol_ok) instead of int16 L
+    int bm_tex;             // BM: texture threshold (minX1 / maxX1 are the BM column range X0 / X1)
+};
+
+// BM: the fused kernel's tiling, chosen on the host (bm.hip bm_plan).
+struct BmPlan {
+    int TX, RB;             // output columns / rows of a workgroup
+    int nsx, nsy;           // grid
+    int waves;              // waves of a workgroup
+    int nk, Dp;             // disparity chunks of 64 per lane, padded row of a column sum (nk * 64)
+    int wide;               // 0: u16 column sums (w^2 * 2c <= 65535), 1: u32
+    int vglobal;            // column sums in the HBM workspace instead of LDS (oversized D x w only)
+    size_t lds;             // dynamic LDS bytes of a workgroup
+    size_t vbytes;          // workspace bytes of the column sums (vglobal)
 };
 
 // OCV workspace: the four u8 prefilter planes, then (256-B aligned) the four u32 planes of

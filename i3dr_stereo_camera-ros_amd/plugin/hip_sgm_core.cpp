@@ -44,6 +44,21 @@ MatcherCore::MatcherCore(int device, int mode) : device_(device)
         mode = env ? std::atoi(env) : SGM_MODE_OCV_SGBM5;
     }
     sgm_default_params(&params_, mode);
+    sgm_default_bm_params(&bm_);
+    if (mode == SGM_MODE_OCV_BM) {
+        // cv::StereoBM::create(64, 9): minDisparity 0, preFilterCap 31 / size 9, texture 10,
+        // uniqueness 15, no speckle filter, disp12MaxDiff -1
+        params_.min_disparity = 0;
+        params_.num_disparities = 64;
+        params_.block_size = 9;
+        params_.prefilter_cap = 31;
+        params_.uniqueness_ratio = 15;
+        params_.speckle_window_size = params_.speckle_range = 0;
+        params_.disp12_max_diff = -1;
+        bm_.texture_threshold = 10;
+        bm_.prefilter_size = 9;
+        return;
+    }
     params_.ocv_compat = ocv_compat_from_env(params_.ocv_compat);
     // cv::StereoSGBM::create(64, 9, 5) (matcherOpenCVSGBM.cpp:14): overwritten by the setters
     params_.min_disparity = 64;
@@ -89,25 +104,39 @@ void MatcherCore::setP2(float p2) { params_.p2 = (int)p2; }
 void MatcherCore::setInterpolation(bool e) { interpolate_ = e; }
 void MatcherCore::setMode(int m) { params_.mode = m; }
 void MatcherCore::setOcvCompat(int bits) { params_.ocv_compat = bits; }
+void MatcherCore::setTextureThreshold(int t) { bm_.texture_threshold = t; }
+void MatcherCore::setPreFilterSize(int s) { bm_.prefilter_size = s; }
 
 sgm_params MatcherCore::rightMatcherParams(const sgm_params& p)
 {
     sgm_params r = p;
     r.min_disparity = -(p.min_disparity + p.num_disparities) + 1;
     r.uniqueness_ratio = 0;
+    if (p.mode == SGM_MODE_OCV_BM) {
+        r.speckle_window_size = r.speckle_range = 0;
+        return r;
+    }
     r.disp12_max_diff = 1000000;
     r.speckle_window_size = 0;
     return r;
 }
 
+sgm_bm_params MatcherCore::rightMatcherBmParams(const sgm_bm_params& b)
+{
+    sgm_bm_params r = b;
+    r.texture_threshold = 0;
+    return r;
+}
+
 // One host-buffer match: float32 output (the CV_32FC1 of matcherOpenCVSGBM.cpp:34, converted
 // on the device by sgm_match_f32) or int16 (CV_16S, the right matcher's disparity_rl).
-int MatcherCore::run(const sgm_params& p, const uint8_t* a, const uint8_t* b, int w, int h, size_t stride, float* outf,
-                     int16_t* out16, size_t out_stride)
+int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t* a, const uint8_t* b, int w, int h,
+                     size_t stride, float* outf, int16_t* out16, size_t out_stride)
 {
     int rc = SGM_OK;
     if (!handle_) rc = sgm_create(&handle_, device_);
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
+    if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
     if (rc == SGM_OK && keep_reg_ && outf) {
         const size_t bytes = out_stride * sizeof(float) * (size_t)(h - 1) + (size_t)w * sizeof(float);
         if (reg_ptr_ != (void*)outf || reg_bytes_ != bytes) {
@@ -121,7 +150,9 @@ int MatcherCore::run(const sgm_params& p, const uint8_t* a, const uint8_t* b, in
                   : sgm_match(handle_, a, b, w, h, stride, out16, out_stride);
     if (rc != SGM_OK) {
         err_ = handle_ ? sgm_last_error(handle_) : "no HIP device";
-        std::cerr << "Error in HIP SGM parameters" << std::endl << err_ << " (status " << rc << ")" << std::endl;
+        // matcherOpenCVBlock.cpp:40 / matcherOpenCVSGBM.cpp:40 style
+        std::cerr << (p.mode == SGM_MODE_OCV_BM ? "Error in HIP StereoBM parameters" : "Error in HIP SGM parameters") << std::endl
+                  << err_ << " (status " << rc << ")" << std::endl;
         return -1;
     }
     return 0;
@@ -132,19 +163,21 @@ int MatcherCore::forwardMatch(const uint8_t* left, const uint8_t* right, int w, 
 {
     if (interpolate_)  // Q3: WLS output discarded, right-view disparity returned
         return backwardMatch(left, right, w, h, stride, out, out_stride);
-    return run(params_, left, right, w, h, stride, out, nullptr, out_stride);
+    return run(params_, bm_, left, right, w, h, stride, out, nullptr, out_stride);
 }
 
 int MatcherCore::backwardMatch(const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, float* out,
                                size_t out_stride)
 {
-    return run(rightMatcherParams(params_), right, left, w, h, stride, out, nullptr, out_stride);
+    return run(rightMatcherParams(params_), rightMatcherBmParams(bm_), right, left, w, h, stride, out, nullptr,
+               out_stride);
 }
 
 int MatcherCore::backwardMatch16(const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, int16_t* out,
                                  size_t out_stride)
 {
-    return run(rightMatcherParams(params_), right, left, w, h, stride, nullptr, out, out_stride);
+    return run(rightMatcherParams(params_), rightMatcherBmParams(bm_), right, left, w, h, stride, nullptr, out,
+               out_stride);
 }
 
 }  // namespace sgm_hip

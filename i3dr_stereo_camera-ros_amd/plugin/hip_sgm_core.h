@@ -23,6 +23,7 @@ class MatcherCore {
 public:
     // mode < 0: SGM_HIP_MODE env var, default SGM_MODE_OCV_SGBM5 (the reference's SGBM
     // path never sets a mode, generate_disparity.cpp:241-261 -> cv::StereoSGBM::MODE_SGBM).
+    // SGM_MODE_OCV_BM (3) starts from cv::StereoBM::create(64, 9) like MatcherOpenCVBlock.
     explicit MatcherCore(int device = 0, int mode = -1);
     ~MatcherCore();
     MatcherCore(const MatcherCore&) = delete;
@@ -42,6 +43,10 @@ public:
     void setInterpolation(bool enable);
     void setMode(int mode);
     void setOcvCompat(int bits);   // SGM_OCV_* (default: SGM_HIP_OCV_COMPAT env, else melodic)
+    // cv::StereoBM only (SGM_MODE_OCV_BM); stored but unused in the other modes, where the
+    // reference's matchers ignore them too (matcherOpenCVSGBM.h:31-34)
+    void setTextureThreshold(int threshold);
+    void setPreFilterSize(int size);
 
     // --- matching -------------------------------------------------------------------
     // u8 mono rectified pair -> CV_32FC1-layout disparity in 1/16 px (x16 fixed point,
@@ -63,17 +68,24 @@ public:
     void releaseOutput();
 
     const sgm_params& params() const { return params_; }
+    const sgm_bm_params& bmParams() const { return bm_; }
     bool interpolation() const { return interpolate_; }
     int disparityRange() const { return params_.num_disparities; }
     const std::string& lastError() const { return err_; }
+    // SGBM modes: cv::ximgproc::createRightMatcher of a StereoSGBM. BM mode: of a StereoBM —
+    // minD' = -(minD + D) + 1, same D and window, uniqueness 0, no speckle filter, and (through
+    // rightMatcherBmParams) texture threshold 0. The BM rule is restated from ximgproc and not
+    // verified against it.
     static sgm_params rightMatcherParams(const sgm_params& p);
+    static sgm_bm_params rightMatcherBmParams(const sgm_bm_params& b);
 
 private:
-    int run(const sgm_params& p, const uint8_t* a, const uint8_t* b, int w, int h, size_t stride, float* outf,
-            int16_t* out16, size_t out_stride);
+    int run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t* a, const uint8_t* b, int w, int h,
+            size_t stride, float* outf, int16_t* out16, size_t out_stride);
     int device_;
     sgm_handle* handle_ = nullptr;   // opened lazily at the first match
     sgm_params params_{};
+    sgm_bm_params bm_{};
     bool interpolate_ = false;
     bool keep_reg_ = false;
     void* reg_ptr_ = nullptr;        // the registered output range

@@ -72,6 +72,8 @@ void MatcherHIPSGM::setDisp12MaxDiff(int diff) { core_.setDisp12MaxDiff(diff); }
 void MatcherHIPSGM::setP1(float p1) { core_.setP1(p1); }
 void MatcherHIPSGM::setP2(float p2) { core_.setP2(p2); }
 void MatcherHIPSGM::setPreFilterCap(int cap) { core_.setPreFilterCap(cap); }
+void MatcherHIPSGM::setTextureThreshold(int threshold) { core_.setTextureThreshold(threshold); }
+void MatcherHIPSGM::setPreFilterSize(int size) { core_.setPreFilterSize(size); }
 
 void MatcherHIPSGM::setInterpolation(bool enable)
 {

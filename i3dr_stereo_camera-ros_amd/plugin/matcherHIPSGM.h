@@ -10,8 +10,10 @@
 class MatcherHIPSGM : public AbstractStereoMatcher
 {
 public:
-  explicit MatcherHIPSGM(std::string &param_file, cv::Size _image_size)
-      : AbstractStereoMatcher(param_file, _image_size), core_(0, -1)
+  // mode: an SGM_MODE_* of sgm_hip.h; -1 reads SGM_HIP_MODE (default SGM_MODE_OCV_SGBM5).
+  // SGM_MODE_OCV_BM (3) makes this the drop-in for MatcherOpenCVBlock (cv::StereoBM).
+  explicit MatcherHIPSGM(std::string &param_file, cv::Size _image_size, int mode = -1)
+      : AbstractStereoMatcher(param_file, _image_size), core_(0, mode)
   {
     init();
   }
@@ -31,9 +33,10 @@ public:
   void setInterpolation(bool enable);
   void setPreFilterCap(int cap);
 
-  // Not used by SGM (no-ops, as matcherOpenCVSGBM.h:31-34)
-  void setTextureThreshold(int threshold){};
-  void setPreFilterSize(int size){};
+  // cv::StereoBM parameters: used in BM mode, ignored by the SGM modes (matcherOpenCVSGBM.h:31-34)
+  void setTextureThreshold(int threshold);
+  void setPreFilterSize(int size);
+  // Not used (no-op)
   void setOcclusionDetection(bool enable){};
 
 private:

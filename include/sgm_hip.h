@@ -34,10 +34,10 @@ extern "C" {
 /* ---- ABI version ------------------------------------------------------------------- */
 /* Bumped whenever a struct or signature of this header changes. Round 3 grew sgm_params
  * from 14 to 15 ints (ocv_compat, version 3); round 4 added sgm_match_tiled_device
- * (version 4). A caller compiled against an older header must check sgm_abi_version()
- * == SGM_ABI_VERSION before passing an sgm_params (a 14-int struct would be read one int
- * past its end).                                                                         */
-#define SGM_ABI_VERSION 4
+ * (version 4); version 5 adds SGM_MODE_OCV_BM with the sgm_bm_params entry points. A caller
+ * compiled against an older header must check sgm_abi_version() == SGM_ABI_VERSION before
+ * passing an sgm_params (a 14-int struct would be read one int past its end).             */
+#define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -56,6 +56,15 @@ int  sgm_abi_version(void);
 #define SGM_MODE_OCV_HH8      1   /* cv::StereoSGBM::MODE_HH: 8 directions (cfg `fullDP`)             */
 /* North-star mode: 9x7 census, Hamming cost, 8 directions, u8 path costs, u16 sums.       */
 #define SGM_MODE_CENSUS8      2
+/* cv::StereoBM, the generate_disparity node's default algorithm (generate_disparity.cpp:98):
+ * XSOBEL pre-filter, SAD block matching, winner-takes-all with texture / uniqueness tests and
+ * the StereoBM sub-pixel formula, optional speckle filter; no path aggregation, no median.
+ * A restatement of OpenCV's scalar findStereoCorrespondenceBM (BM section),
+ * unverified against a real OpenCV. Uses sgm_params' min_disparity, num_disparities,
+ * block_size, prefilter_cap, uniqueness_ratio, speckle_*, disp12_max_diff (must be < 0: off)
+ * plus sgm_bm_params; p1, p2, subpixel, lr_check, median and ocv_compat are ignored. Nothing
+ * is repaired in this mode: invalid values are SGM_ERR_PARAM at match time.                */
+#define SGM_MODE_OCV_BM       3
 
 /* OpenCV build variants of the OCV modes (`sgm_params.ocv_compat`, a bitfield). The reference
  * pins OpenCV only through its ROS distro — melodic (OpenCV 3.2.0, the reference's Dockerfile:1,
@@ -89,12 +98,20 @@ typedef struct sgm_params {
     int disp12_max_diff;      /* setDisp12MaxDiff (<=0 -> 1, as OpenCV SGBM)              */
     int prefilter_cap;        /* setPreFilterCap (OCV modes)                              */
     int speckle_window_size;  /* setSpeckleFilterWindow (0 = speckle filter off)          */
-    int speckle_range;        /* setSpeckleFilterRange (max diff in pixels; x16 internally) */
+    int speckle_range;        /* setSpeckleFilterRange (max diff in pixels; x16 internally; BM mode: unscaled) */
     int subpixel;             /* census: parabolic 1/16 interpolation on/off (OCV: always on) */
     int lr_check;             /* census: left-right (disp2) check on/off (OCV: always on)     */
     int median;               /* census: 3x3 median post-filter on/off (OCV: always on)       */
     int ocv_compat;           /* OCV modes: SGM_OCV_* bits of the OpenCV build to reproduce   */
 } sgm_params;
+
+/* The two cv::StereoBM parameters sgm_params has no field for (sgm_params stays 15 ints).
+ * prefilter_size is validated (odd, 5..255) but otherwise unused: the pre-filter type is
+ * always PREFILTER_XSOBEL, which the reference never changes.                              */
+typedef struct sgm_bm_params {
+    int texture_threshold;    /* setTextureThreshold (cfg texture_threshold), >= 0           */
+    int prefilter_size;       /* setPreFilterSize    (cfg prefilter_size)                    */
+} sgm_bm_params;
 
 typedef struct sgm_handle sgm_handle;
 
@@ -125,6 +142,13 @@ int  sgm_host_unregister(sgm_handle* h, void* ptr);
  * OCV modes = the generate_disparity node defaults (generate_disparity.cpp:100-112) and
  * ocv_compat = SGM_OCV_COMPAT_MELODIC (the OpenCV the reference's Dockerfile:1 ships).     */
 void sgm_default_params(sgm_params* p, int mode);
+/* SGM_MODE_OCV_BM defaults: sgm_default_params gives the node's values (min_disparity 9,
+ * num_disparities 64, block_size 15, uniqueness 15, prefilter_cap 31, speckles 100 / 4,
+ * disp12_max_diff -1); the BM-only pair defaults to texture_threshold 10, prefilter_size 9. */
+void sgm_default_bm_params(sgm_bm_params* p);
+/* The BM-only parameters of a handle (used by SGM_MODE_OCV_BM matches only).                */
+int  sgm_set_bm_params(sgm_handle* h, const sgm_bm_params* p);
+int  sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p);
 
 /* Store parameters. Like the reference's setters this never fails on values; invalid
  * combinations surface at match time (matcherOpenCVSGBM.cpp:37-43 behaviour).            */
@@ -133,6 +157,9 @@ int  sgm_get_params(const sgm_handle* h, sgm_params* p);
 
 /* Validate parameters for a W-wide image without matching (0 = would run).                */
 int  sgm_check_params(const sgm_params* p, int width, int height);
+/* The same for SGM_MODE_OCV_BM with explicit BM parameters (sgm_check_params validates that
+ * mode with sgm_default_bm_params).                                                        */
+int  sgm_check_bm_params(const sgm_params* p, const sgm_bm_params* bm, int width, int height);
 
 /* ---- matching -------------------------------------------------------------------------- */
 /* Host buffers in, host buffer out; synchronous. L/R: W x H u8 mono (stride bytes);
@@ -313,6 +340,16 @@ int  sgm_debug_census_path(sgm_handle* h, const uint8_t* left, const uint8_t* ri
  * layout [H][width1][D].                                                                  */
 int  sgm_debug_ocv_cost(sgm_handle* h, const uint8_t* left, const uint8_t* right,
                         int width, int height, size_t stride, int16_t* cost);
+/* BM mode: the XSOBEL pre-filtered image (host u8 in, W x H u8 out, row-major).             */
+int  sgm_debug_bm_prefilter(sgm_handle* h, const uint8_t* img, int width, int height, size_t stride,
+                            uint8_t* out);
+/* BM mode, small frames: the int32 SAD volume of the fused kernel, layout [H][X1 - X0][D]
+ * with X0 = max(D - 1 + minD, 0), X1 = min(W, W + minD), and the int32 texture plane
+ * [H][X1 - X0]. The last index is e = D - 1 - (d - minD): e = 0 is the LARGEST disparity
+ * minD + D - 1, the order OpenCV's inner loop scans. Rows outside [w/2, H - w/2) are 0.
+ * Either output may be NULL. SGM_ERR_UNSUPPORTED above 2^27 volume cells.                  */
+int  sgm_debug_bm_sad(sgm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
+                      size_t stride, int32_t* sad, int32_t* texture);
 /* Census mode: the path work list one launch would dispatch (host-only, no device): every
  * 16-line block of the directions in dir_mask (bit d) of `group` frames, plus the up+WTA
  * blocks (code 8) of `up_group` frames, as dir << 24 | frame << 22 | block, longest first,
