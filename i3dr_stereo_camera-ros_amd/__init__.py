@@ -62,6 +62,22 @@ def ocv_compat_from_env(default=COMPAT_MELODIC):
         sys.stderr.write(f'SGM_HIP_OCV_COMPAT="{raw}" is not melodic | noetic | scalar | <bits>: using {default}\n')
         return default
 
+
+def census_paths_from_env(default=8):
+    """SGM_HIP_CENSUS_PATHS = 4 | 8: the census mode's path set (the C++ adapter core reads the same
+    variable). Any integer is passed on (one other than 4 or 8 fails at match
+    time); an unparseable value warns and keeps the default, as hip_sgm_core.cpp does."""
+    raw = os.environ.get("SGM_HIP_CENSUS_PATHS")
+    v = (raw or "").strip(" \t\n\v\f\r")
+    if not v:
+        return default
+    body = v[1:] if v[0] in "+-" else v
+    if not (body.isascii() and body.isdigit()) or abs(int(v)) > 1000000:
+        sys.stderr.write(f'SGM_HIP_CENSUS_PATHS="{raw}" is not 4 or 8: using {default}\n')
+        return default
+    return int(v)
+
+
 EXPORTS = [
     "sgm_device_count", "sgm_create", "sgm_destroy", "sgm_default_params", "sgm_set_params", "sgm_get_params",
     "sgm_check_params", "sgm_match", "sgm_match_f32", "sgm_match_device", "sgm_match_device_batch", "sgm_match_batch", "sgm_match_tiled",
@@ -71,7 +87,7 @@ EXPORTS = [
     "sgm_remap_cubic", "sgm_cubic_table", "sgm_set_rectification", "sgm_match_device_batch_rect", "sgm_debug_census",
     "sgm_debug_census_path", "sgm_debug_ocv_cost", "sgm_debug_median3", "sgm_debug_speckle", "sgm_debug_path_items",
     "sgm_default_bm_params", "sgm_set_bm_params", "sgm_get_bm_params", "sgm_check_bm_params", "sgm_debug_bm_prefilter",
-    "sgm_debug_bm_sad",
+    "sgm_debug_bm_sad", "sgm_set_census_paths", "sgm_get_census_paths",
 ]
 
 
@@ -187,6 +203,8 @@ def load_library(path=None):
     L.sgm_set_bm_params.argtypes = [vp, P(BmParams)]
     L.sgm_get_bm_params.argtypes = [vp, P(BmParams)]
     L.sgm_check_bm_params.argtypes = [P(SgmParams), P(BmParams), ci, ci]
+    L.sgm_set_census_paths.argtypes = [vp, ci]
+    L.sgm_get_census_paths.argtypes = [vp, P(ci)]
     L.sgm_debug_bm_prefilter.argtypes = [vp, vp, ci, ci, sz, vp]
     L.sgm_debug_bm_sad.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
     _lib = L
@@ -290,6 +308,16 @@ class Engine:
         b = BmParams()
         self._check(self.lib.sgm_get_bm_params(self.h, ctypes.byref(b)))
         return b
+
+    def set_census_paths(self, paths):
+        """Census mode: 8 aggregation paths (default) or 4 (down, up, left, right). Stored as given;
+        a value other than 4 or 8 fails at match time."""
+        self._check(self.lib.sgm_set_census_paths(self.h, int(paths)))
+
+    def get_census_paths(self):
+        n = ctypes.c_int()
+        self._check(self.lib.sgm_get_census_paths(self.h, ctypes.byref(n)))
+        return n.value
 
     def match(self, left, right):
         left = np.ascontiguousarray(left, np.uint8)
@@ -677,9 +705,11 @@ class MatcherHIPSGM:
     MatcherOpenCVSGBM (matcherOpenCVSGBM.{h,cpp}); compute delegated to libsgm_hip.so.
     `mode` picks the engine mode (the reference's SGBM path never sets a mode, Q1, so the
     OpenCV-compatible default is MODE_SGBM = 5 directions; env SGM_HIP_MODE overrides).
+    `census_paths` (census mode only): 8 or 4 aggregation paths; None reads env
+    SGM_HIP_CENSUS_PATHS (default 8).
     """
 
-    def __init__(self, param_file=" ", image_size=(0, 0), device=0, mode=None):
+    def __init__(self, param_file=" ", image_size=(0, 0), device=0, mode=None, census_paths=None):
         self.param_file = param_file
         self.image_size = (0, 0)          # Q5: the base ctor ignores _image_size
         self.downsample_scale = 1.0
@@ -695,6 +725,7 @@ class MatcherHIPSGM:
             mode = int(os.environ.get("SGM_HIP_MODE", MODE_OCV_SGBM5))
         self.device = device
         self.mode = mode
+        self.census_paths = census_paths_from_env(8) if census_paths is None else int(census_paths)
         self.init()
 
     # --- AbstractStereoMatcher ----------------------------------------------------------
@@ -786,6 +817,7 @@ class MatcherHIPSGM:
     def _run(self, params, a, b, f32=False, bm=None):
         eng = self._engine_for()
         eng.set_params(params)
+        eng.set_census_paths(self.census_paths)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm if bm is not None else self.bm_params)
         return eng.match_f32(a, b) if f32 else eng.match(a, b)

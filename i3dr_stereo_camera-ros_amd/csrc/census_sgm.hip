@@ -7,6 +7,9 @@
 //                                      one launch (6 row sweeps + 2 horizontal scans)
 //   k_census_wta      8 volumes     -> S = sum of the 8 paths, WTA, uniqueness, subpixel,
 //                                      disp2 and LR check (one workgroup per row)
+// The 4-path set (sgm_set_census_paths: dirs 0, 1, 6, 7) runs the same kernels with the number
+// of summed volumes NP = 4 as a template parameter and four compact slices per volume set
+// (sgm_device.h vol_slot).
 // The matching cost popcount(cL ^ cR) is recomputed on the fly in every path (never
 // stored); S never touches HBM.
 #include "sgm_device.h"
@@ -582,7 +585,9 @@ __host__ __device__ constexpr size_t upwta_lds_bytes() { return (size_t)8 * 2 * 
 
 // NL lines of direction dir starting at base column xb (DPL disparities per lane, LPL
 // lanes per line; lds: 2 * RowSeg<DPL, LPL>::BUF codes).
-template <int DPL, bool EXACT, int LPL, bool FUSE = false, bool PRIO = false>
+// NP (FUSE only): paths summed by the WTA (8, or 4: dirs 0, 1, 6, 7 in compact slots), so the
+// step loads the NP - 1 stored volumes of slots 0, 2, 3, .. (slot 1, dir 1, is never written).
+template <int DPL, bool EXACT, int LPL, bool FUSE = false, bool PRIO = false, int NP = 8>
 __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const uint64_t* __restrict__ cR,
                                          uint8_t* __restrict__ V, uint8_t* __restrict__ trash, const Geom& g, int dir,
                                          int xb, const PathLaunch16& pl, uint64_t* lds, const UpWta& uw = UpWta{})
@@ -641,9 +646,10 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     seg_load<DPL, LPL>(R3, sa, g, rx, ry, xb, min(s0 + 3, s1 - 1));
     __syncthreads();
 
-    // up+WTA (FUSE): the seven other volumes of the line's pixel, loaded one step ahead
+    // up+WTA (FUSE): the NP - 1 other volumes of the line's pixel, loaded one step ahead
     constexpr int NWD = (DPL + 3) / 4;
-    uint32_t vw[7][NWD], emaskE[NWD], emaskO[NWD];
+    constexpr int NV = NP - 1;
+    uint32_t vw[NV][NWD], emaskE[NWD], emaskO[NWD];
     uint32_t* srow = (uint32_t*)(lds + 2 * RS::BUF) + j * 32 * NWD;
     const float inv_u = 1.0f / (float)max(100 - g.uniq, 1);
     const uint32_t voff = (uint32_t)((min(max(xb + j, g.minX1), g.maxX1 - 1) - g.minX1) * g.D + (lane_act ? p * DPL : 0));
@@ -654,7 +660,7 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     auto vload = [&](int s) {
         const uint8_t* rb = (const uint8_t*)vols0 + (size_t)max(g.H - 1 - s, 0) * g.width1 * g.D;   // wave-uniform
 #pragma unroll
-        for (int k = 0; k < 7; k++) wload_buf<DPL>(rb + (size_t)(k == 0 ? 0 : k + 1) * uw.vol_bytes, voff, vw[k]);
+        for (int k = 0; k < NV; k++) wload_buf<DPL>(rb + (size_t)(k == 0 ? 0 : k + 1) * uw.vol_bytes, voff, vw[k]);
     };
     if constexpr (FUSE) {
         wta_emask<DPL, EXACT>(p, g, emaskE, emaskO);
@@ -668,16 +674,16 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
         const uint64_t cl = bufc[RS::NPAD + j];
         uint32_t Labs[M];
         uint32_t E[NWD], O[NWD];
-        if constexpr (FUSE) {       // this step's seven costs, then the next step's loads
+        if constexpr (FUSE) {       // this step's NP - 1 costs, then the next step's loads
 #pragma unroll
             for (int jj = 0; jj < NWD; jj++) {
                 uint32_t e = 0, o = 0;
 #pragma unroll
-                for (int k = 0; k < 7; k++) {
+                for (int k = 0; k < NV; k++) {
                     e += vw[k][jj] & 0x00FF00FFu;
                     o += __builtin_amdgcn_perm(0u, vw[k][jj], 0x0c030c01u);
                 }
-                asm("" : "+v"(e), "+v"(o));     // the sums, not 14 extracted words, stay live
+                asm("" : "+v"(e), "+v"(o));     // the sums, not 2 * NV extracted words, stay live
                 E[jj] = e;
                 O[jj] = o;
             }
@@ -744,7 +750,8 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
 template <int DPL>
 __host__ __device__ constexpr int rows_lds_codes() { return 2 * RowSeg<RowsCfg<DPL>::DPL, RowsCfg<DPL>::LPL>::BUF; }
 
-template <int DPL, bool EXACT, bool PRIO = false>
+// NP: the launch's path set when it is a compile-time constant (the fused launches), 0: pf.np.
+template <int DPL, bool EXACT, bool PRIO = false, int NP = 0>
 __device__ __forceinline__ void paths_block16(const PathFrames& pf, size_t vol_bytes, size_t trash_off,
                                               const Geom& g, const PathLaunch16& pl, uint32_t it, uint64_t* lds)
 {
@@ -756,7 +763,7 @@ __device__ __forceinline__ void paths_block16(const PathFrames& pf, size_t vol_b
     if (f >= pf.n || ((pf.skip_dirs >> dir) & 1u)) return;    // uniform over the workgroup
     const uint64_t* cL = pick4(pf.cL, f);
     const uint64_t* cR = pick4(pf.cR, f);
-    uint8_t* V = pick4(pf.vols, f) + (size_t)dir * vol_bytes;
+    uint8_t* V = pick4(pf.vols, f) + (size_t)vol_slot(NP ? NP : pf.np, dir) * vol_bytes;
     uint8_t* trash = V + trash_off;
     const int y0 = lb * HC::HROWS + (64 / HC::LPL) * (threadIdx.x >> 6);
     if (dir == 6) p16_horiz<HC::DPL, EXACT, 1, PRIO, HC::LPL>(cL, cR, V, trash, g, y0);
@@ -909,7 +916,8 @@ __device__ __forceinline__ void wta_emask(int p, const Geom& g, uint32_t (&emask
 }
 
 // One image row y (one workgroup). lds: wta_lds_bytes<DPL>(W) bytes.
-template <int DPL, bool EXACT, typename OutT = int16_t>
+// NP: volumes summed (slots 0 .. NP-1 of the set)
+template <int DPL, bool EXACT, int NP, typename OutT = int16_t>
 __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size_t vol_bytes, const Geom& g,
                                           OutT* __restrict__ out, size_t out_stride, int y, uint32_t* lds)
 {
@@ -937,10 +945,10 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
     // Buffer loads (one descriptor per volume from the wave-uniform group base, the lane's
     // offset in a VGPR): no per-lane 64-bit address arithmetic.
     const uint32_t loff = off0 + (uint32_t)(r * g.D);
-    auto load = [&](int q, uint32_t (&v)[8][NWD]) {
+    auto load = [&](int q, uint32_t (&v)[NP][NWD]) {
         const uint8_t* rowq = vols + row0 + (size_t)(4 * q) * g.D;
 #pragma unroll
-        for (int vv = 0; vv < 8; vv++) {
+        for (int vv = 0; vv < NP; vv++) {
             if ((SGM_EXP & 4) && vv == 1) { for (int j = 0; j < NWD; j++) v[vv][j] = 0; continue; }
             wload_buf<DPL>(rowq + (size_t)vv * vol_bytes, loff, v[vv]);
         }
@@ -948,12 +956,12 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
     // S in u16 pairs (wta_pix16). The next pixel group's loads are summed at the end of an
     // iteration, so only one set of raw volume words is live.
     uint32_t E[NWD], O[NWD];
-    auto sum8 = [&](const uint32_t (&v)[8][NWD]) {
+    auto sum8 = [&](const uint32_t (&v)[NP][NWD]) {
 #pragma unroll
         for (int j = 0; j < NWD; j++) {
             uint32_t e = 0, o = 0;
 #pragma unroll
-            for (int vv = 0; vv < 8; vv++) {
+            for (int vv = 0; vv < NP; vv++) {
                 e += v[vv][j] & 0x00FF00FFu;
                 o += __builtin_amdgcn_perm(0u, v[vv][j], 0x0c030c01u);
             }
@@ -961,7 +969,7 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
             O[j] = o | emaskO[j];
         }
     };
-    uint32_t nxt[8][NWD];
+    uint32_t nxt[NP][NWD];
     load(min(w, nq - 1), nxt);
     sum8(nxt);
     for (int q = w; q < nq; q += 4) {
@@ -981,30 +989,30 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
 }
 
 // block b: row b % H of frame b / H
-template <int DPL, bool EXACT>
+template <int DPL, bool EXACT, int NP>
 __device__ __forceinline__ void wta_block16(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride,
                                             int b, uint32_t* lds)
 {
     const int f = b / g.H;
-    wta_row16<DPL, EXACT>(pick4(wf.vols, f), vol_bytes, g, pick4(wf.out, f), out_stride, b - f * g.H, lds);
+    wta_row16<DPL, EXACT, NP>(pick4(wf.vols, f), vol_bytes, g, pick4(wf.out, f), out_stride, b - f * g.H, lds);
 }
 
-template <int DPL, bool EXACT>
+template <int DPL, bool EXACT, int NP>
 __global__ __launch_bounds__(kWG) void k_census_wta16(WtaFrames wf, size_t vol_bytes, Geom g, size_t out_stride)
 {
     extern __shared__ uint32_t lds_dyn[];
-    wta_block16<DPL, EXACT>(wf, vol_bytes, g, out_stride, blockIdx.x, lds_dyn);
+    wta_block16<DPL, EXACT, NP>(wf, vol_bytes, g, out_stride, blockIdx.x, lds_dyn);
 }
 
 // The same for one frame whose rows go out as float (the node's CV_32FC1) straight into a host
 // buffer mapped into the device's address space: the row stores cross PCIe while the other rows'
 // volume reads run, instead of a to-float kernel and an 8 MB copy after the frame (the node's
 // host call, matcherOpenCVSGBM.cpp:34 / generate_disparity.cpp:350-357).
-template <int DPL, bool EXACT>
+template <int DPL, bool EXACT, int NP>
 __global__ __launch_bounds__(kWG) void k_census_wta16f(WtaFrames wf, size_t vol_bytes, Geom g)
 {
     extern __shared__ uint32_t lds_dyn[];
-    wta_row16<DPL, EXACT, float>(wf.vols[0], vol_bytes, g, wf.outf[0], wf.outf_stride, blockIdx.x, lds_dyn);
+    wta_row16<DPL, EXACT, NP, float>(wf.vols[0], vol_bytes, g, wf.outf[0], wf.outf_stride, blockIdx.x, lds_dyn);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1070,7 +1078,7 @@ __global__ __launch_bounds__(kWG) void k_census_tiles(CensusFrames cf, int W, in
 
 // blocks: [0, n_items) path items of pf | H * wf.n WTA rows of wf | census blocks of cf.
 // wta_rows = 0: wf is served by up+WTA items (dir 8) of the work list instead of WTA rows.
-template <int DPL, bool EXACT>
+template <int DPL, bool EXACT, int NP>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(DPL >= 32 ? SGM_WPE32 : SGM_WPE)))
 void k_census_fused16(PathFrames pf, WtaFrames wf, CensusFrames cf, size_t vol_bytes, size_t trash_off, Geom g,
                       PathLaunch16 pl, const uint32_t* __restrict__ items, int n_items, size_t out_stride,
@@ -1096,7 +1104,7 @@ void k_census_fused16(PathFrames pf, WtaFrames wf, CensusFrames cf, size_t vol_b
     if (kind == 0) {
         const uint32_t it = items[idx];
         if constexpr (DPL > 16) {           // D > 256: no up+WTA items (host layout)
-            paths_block16<DPL, EXACT>(pf, vol_bytes, trash_off, g, pl, it, lds_dyn64);
+            paths_block16<DPL, EXACT, false, NP>(pf, vol_bytes, trash_off, g, pl, it, lds_dyn64);
         } else if ((it >> 24) == 8u) {      // up+WTA of frame f of wf
             const int f = (int)((it >> 22) & 3u);
             if (f < wf.n) {
@@ -1104,14 +1112,14 @@ void k_census_fused16(PathFrames pf, WtaFrames wf, CensusFrames cf, size_t vol_b
                 __builtin_amdgcn_s_setprio(SGM_UPWTA_PRIO);   // the launch's longest blocks
 #endif
                 const UpWta uw{pick4(wf.vols, f), vol_bytes, pick4(wf.res, f)};
-                p16_rows<DPL, EXACT, 16, true>(pick4(wf.cL, f), pick4(wf.cR, f), nullptr, nullptr, g, 1,
+                p16_rows<DPL, EXACT, 16, true, false, NP>(pick4(wf.cL, f), pick4(wf.cR, f), nullptr, nullptr, g, 1,
                                                pl.xb_lo[1] + (int)(it & 0x3FFFFFu) * 16, pl, lds_dyn64, uw);
             }
         } else {
-            paths_block16<DPL, EXACT>(pf, vol_bytes, trash_off, g, pl, it, lds_dyn64);
+            paths_block16<DPL, EXACT, false, NP>(pf, vol_bytes, trash_off, g, pl, it, lds_dyn64);
         }
     } else if (kind == 1) {
-        wta_block16<DPL, EXACT>(wf, vol_bytes, g, out_stride, idx, (uint32_t*)lds_dyn64);
+        wta_block16<DPL, EXACT, NP>(wf, vol_bytes, g, out_stride, idx, (uint32_t*)lds_dyn64);
     } else {
         census_block(cf, g.W, g.H, idx, (uint8_t*)lds_dyn64);
     }
@@ -1300,38 +1308,47 @@ hipError_t launch_census_paths(const PathFrames& pf, size_t vol_bytes, const Geo
     return hipGetLastError();
 }
 
-template <int DPL>
+template <int DPL, int NP>
 static void launch_wta_dpl(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st)
 {
     dim3 grid(g.H * wf.n), block(kWG);
     const size_t lds = wta_lds_bytes<DPL>(g.W);
     if (wf.outf[0]) {                  // one frame, float rows into a mapped host buffer
         if (g.D == 16 * DPL)
-            hipLaunchKernelGGL((k_census_wta16f<DPL, true>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
+            hipLaunchKernelGGL((k_census_wta16f<DPL, true, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
         else
-            hipLaunchKernelGGL((k_census_wta16f<DPL, false>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
+            hipLaunchKernelGGL((k_census_wta16f<DPL, false, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
         return;
     }
     if (g.D == 16 * DPL)
-        hipLaunchKernelGGL((k_census_wta16<DPL, true>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
+        hipLaunchKernelGGL((k_census_wta16<DPL, true, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
     else
-        hipLaunchKernelGGL((k_census_wta16<DPL, false>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
+        hipLaunchKernelGGL((k_census_wta16<DPL, false, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
 }
 
-// WTA + LR of the frames in wf (volumes -> disparity).
-hipError_t launch_census_wta(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st)
+template <int NP>
+static void launch_wta_np(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st)
 {
     switch (dpl16_for(g.D)) {
-    case 2: launch_wta_dpl<2>(wf, vol_bytes, g, out_stride, st); break;
-    case 4: launch_wta_dpl<4>(wf, vol_bytes, g, out_stride, st); break;
-    case 8: launch_wta_dpl<8>(wf, vol_bytes, g, out_stride, st); break;
-    case 16: launch_wta_dpl<16>(wf, vol_bytes, g, out_stride, st); break;
-    default: launch_wta_dpl<32>(wf, vol_bytes, g, out_stride, st); break;
+    case 2: launch_wta_dpl<2, NP>(wf, vol_bytes, g, out_stride, st); break;
+    case 4: launch_wta_dpl<4, NP>(wf, vol_bytes, g, out_stride, st); break;
+    case 8: launch_wta_dpl<8, NP>(wf, vol_bytes, g, out_stride, st); break;
+    case 16: launch_wta_dpl<16, NP>(wf, vol_bytes, g, out_stride, st); break;
+    default: launch_wta_dpl<32, NP>(wf, vol_bytes, g, out_stride, st); break;
     }
+}
+
+// WTA + LR of the frames in wf (volumes -> disparity). np: paths summed (8, or 4: the compact
+// slots of dirs 0, 1, 6, 7).
+hipError_t launch_census_wta(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st,
+                             int np)
+{
+    if (np == 4) launch_wta_np<4>(wf, vol_bytes, g, out_stride, st);
+    else launch_wta_np<8>(wf, vol_bytes, g, out_stride, st);
     return hipGetLastError();
 }
 
-template <int DPL>
+template <int DPL, int NP>
 static void launch_fused_dpl(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
                              size_t trash_off, const Geom& g, const PathLaunch16& pl, const uint32_t* items,
                              int n_items, size_t out_stride, bool up_wta, hipStream_t st)
@@ -1348,10 +1365,10 @@ static void launch_fused_dpl(const PathFrames& pf, const WtaFrames& wf, const Ce
     // instead of waiting for the sweeps' tail
     static const int period = getenv("SGM_WTA_PERIOD") ? (int)(16 * atof(getenv("SGM_WTA_PERIOD"))) : 40;
     if (g.D == 16 * DPL)
-        hipLaunchKernelGGL((k_census_fused16<DPL, true>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
+        hipLaunchKernelGGL((k_census_fused16<DPL, true, NP>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
                            pl, items, n_items, out_stride, period, up_wta ? 0 : 1, tr);
     else
-        hipLaunchKernelGGL((k_census_fused16<DPL, false>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
+        hipLaunchKernelGGL((k_census_fused16<DPL, false, NP>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
                            pl, items, n_items, out_stride, period, up_wta ? 0 : 1, tr);
     trace_dump(tr, (int)grid.x, st);
 }
@@ -1363,24 +1380,35 @@ hipError_t launch_census_tiles(const CensusFrames& cf, int W, int H, hipStream_t
     return hipGetLastError();
 }
 
+template <int NP>
+static void launch_fused_np(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
+                            const Geom& g, const uint32_t* items, int n_items, size_t out_stride, bool up_wta,
+                            hipStream_t st)
+{
+    const PathLaunch16 pl = make_path_launch16(g);
+    const size_t trash_off = (size_t)g.H * g.width1 * g.D;
+    switch (dpl16_for(g.D)) {
+    case 2: launch_fused_dpl<2, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
+    case 4: launch_fused_dpl<4, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
+    case 8: launch_fused_dpl<8, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
+    case 16: launch_fused_dpl<16, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
+    default: launch_fused_dpl<32, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
+    }
+}
+
 // One launch: path sweeps of the frames in pf (items), WTA of the frames in wf (the previous
 // group) and census of the frames in cf (the next group). Any of the three may be empty
 // (n_items = 0, wf.n = 0, cf.n = 0). All volume sets have the same geometry. up_wta: the
 // work list carries up+WTA items for wf (its dir-1 sweeps; wf.res receives the results, and
 // launch_census_rowfin finishes the rows) instead of WTA rows.
+// The path set of the launch is pf.np (8, or 4: the items list dirs 0, 1, 6, 7 only and every
+// volume set has four slices).
 hipError_t launch_census_fused(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
                                const Geom& g, const uint32_t* items, int n_items, size_t out_stride, bool up_wta,
                                hipStream_t st)
 {
-    const PathLaunch16 pl = make_path_launch16(g);
-    const size_t trash_off = (size_t)g.H * g.width1 * g.D;
-    switch (dpl16_for(g.D)) {
-    case 2: launch_fused_dpl<2>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 4: launch_fused_dpl<4>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 8: launch_fused_dpl<8>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 16: launch_fused_dpl<16>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    default: launch_fused_dpl<32>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    }
+    if (pf.np == 4) launch_fused_np<4>(pf, wf, cf, vol_bytes, g, items, n_items, out_stride, up_wta, st);
+    else launch_fused_np<8>(pf, wf, cf, vol_bytes, g, items, n_items, out_stride, up_wta, st);
     return hipGetLastError();
 }
 

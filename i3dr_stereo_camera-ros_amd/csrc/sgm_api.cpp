@@ -29,7 +29,7 @@ int census_path_items(const Geom&, unsigned, int, int, uint32_t*, int, int up_gr
 int census_vol_group(int D);
 hipError_t launch_census_paths(const PathFrames&, size_t, const Geom&, const uint32_t*, int, hipStream_t,
                                const uint8_t* = nullptr, const uint8_t* = nullptr, size_t = 0);
-hipError_t launch_census_wta(const WtaFrames&, size_t, const Geom&, size_t, hipStream_t);
+hipError_t launch_census_wta(const WtaFrames&, size_t, const Geom&, size_t, hipStream_t, int np = 8);
 hipError_t launch_rectify_map(const double*, const double*, const double*, int, int, float*, float*, size_t,
                               hipStream_t);
 hipError_t launch_remap_cubic(const uint8_t*, size_t, int, int, const float*, const float*, size_t, int, int,
@@ -212,6 +212,7 @@ struct sgm_handle {
     int device = 0;
     sgm_params params{};
     sgm_bm_params bm = kBmDefaults;   // SGM_MODE_OCV_BM only
+    int census_paths = 8;             // SGM_MODE_CENSUS8 only: 8, or 4 (sgm_set_census_paths)
     hipStream_t stream = nullptr;
     std::string err;
     std::mutex mu;
@@ -387,6 +388,7 @@ struct Layout {
     size_t cL[3 * sgm::kMaxGroup] = {}, cR[3 * sgm::kMaxGroup] = {}, vols[2 * sgm::kMaxGroup] = {};
     size_t res[sgm::kMaxGroup] = {};
     size_t vol_bytes = 0;
+    int np = 8;                                            // census path set: slices per volume set
     int group = 1;                                         // frames per pipelined launch
     bool up_wta = false;                                   // pipelined batch: up+WTA scheme
     size_t items[2] = {}; int n_items[2] = {};             // path work lists: one frame / a group
@@ -408,9 +410,10 @@ bool use_up_wta()
     return !e || std::atoi(e) != 0;
 }
 
-Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0, int n_cu = 0)
+Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0, int n_cu = 0, int np = 8)
 {
     Layout l;
+    l.np = np == 4 ? 4 : 8;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1)); return o; };
     auto take_codes = [&](size_t n) { return take((n + 2 * sgm::kCodeMargin) * 8) + 8 * sgm::kCodeMargin; };
@@ -432,7 +435,8 @@ Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group =
         // blocks are long latency-bound chains (C5 batch: 32.3 vs 23.3 ms per frame)
         l.up_wta = group > 0 && use_up_wta() && g.D <= 256;
         const int sets = group > 0 ? 2 * l.group : 1;
-        for (int i = 0; i < sets; i++) l.vols[i] = take(l.vol_bytes * 8);
+        for (int i = 0; i < sets; i++) l.vols[i] = take(l.vol_bytes * l.np);
+        const unsigned mask = sgm::census_dir_mask(l.np);
         for (int i = 0; i < (l.up_wta ? 3 * l.group : sets); i++) {
             l.cL[i] = take_codes(WH);
             l.cR[i] = take_codes(WH);
@@ -440,10 +444,10 @@ Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group =
         if (l.up_wta)
             for (int i = 0; i < l.group; i++) l.res[i] = take((WH + 64) * 8);
         if (g.width1 > 0) {
-            l.n_items[0] = sgm::census_path_items(g, 0xFFu, 1, 1, nullptr, 0);
+            l.n_items[0] = sgm::census_path_items(g, mask, 1, 1, nullptr, 0);
             l.items[0] = take((size_t)l.n_items[0] * 4);
             if (group > 0) {
-                l.n_items[1] = sgm::census_path_items(g, 0xFFu, 1, l.group, nullptr, 0, l.up_wta ? l.group : 0);
+                l.n_items[1] = sgm::census_path_items(g, mask, 1, l.group, nullptr, 0, l.up_wta ? l.group : 0);
                 l.items[1] = take((size_t)l.n_items[1] * 4);
             }
         }
@@ -501,8 +505,8 @@ int path_items(sgm_handle* h, const Layout& l, const Geom& g, unsigned dir_mask,
     uint32_t* d = (uint32_t*)((char*)h->ws.base + l.items[w]);
     *dev = d;
     char key[160];
-    snprintf(key, sizeof key, "%d %d %d %d %x %d %d %d %p", g.W, g.H, g.D, g.minD, dir_mask, group, up_group, h->n_cu,
-             (void*)d);
+    snprintf(key, sizeof key, "%d %d %d %d %x %d %d %d %d %p", g.W, g.H, g.D, g.minD, dir_mask, group, up_group, h->n_cu,
+             l.np, (void*)d);
     const int n = sgm::census_path_items(g, dir_mask, h->n_cu, group, nullptr, 0, up_group);
     if (h->items_key[w] == key) return n;
     if (n > l.n_items[w]) return fail(h, SGM_ERR_ARG, "path work list larger than its workspace slot");
@@ -613,17 +617,17 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
             HIP_TRY(sgm::launch_census(dL, dR, stride, g.W, g.H, cL, cR, st), "census");
         }
         const uint32_t* items;
-        const int n_items = path_items(h, l, g, 0xFFu, 1, st, &items);
+        const int n_items = path_items(h, l, g, sgm::census_dir_mask(l.np), 1, st, &items);
         if (n_items < 0) return n_items;
         sgm::PathFrames pf{};
-        pf.cL[0] = cL; pf.cR[0] = cR; pf.vols[0] = vols; pf.n = 1;
+        pf.cL[0] = cL; pf.cR[0] = cR; pf.vols[0] = vols; pf.n = 1; pf.np = l.np;
         sgm::WtaFrames wf{};
         wf.vols[0] = vols; wf.out[0] = dst; wf.n = 1;
         if (outf) { wf.outf[0] = outf; wf.outf_stride = outf_stride; }
-        rec.begin("paths8", 8 * cells);
+        rec.begin(l.np == 4 ? "paths4" : "paths8", l.np * cells);
         HIP_TRY(sgm::launch_census_paths(pf, l.vol_bytes, g, items, n_items, st), "paths");
-        rec.begin("wta_lr", 8 * cells + 2 * WH);
-        HIP_TRY(sgm::launch_census_wta(wf, l.vol_bytes, g, dst_stride, st), "wta");
+        rec.begin("wta_lr", l.np * cells + 2 * WH);
+        HIP_TRY(sgm::launch_census_wta(wf, l.vol_bytes, g, dst_stride, st, l.np), "wta");
     } else {
         const int fullDP = p.mode == SGM_MODE_OCV_HH8;
         const int mask = fullDP ? 0xFF : 0xCD;   // SGBM5: dirs 0,2,3,6,7
@@ -706,6 +710,8 @@ int batch_group(int n)
 //   ... | wta(Glast) post
 // The census of group k+1 writes the code set of group k-1, whose path sweeps finished in
 // the previous launch.
+// With 4 census paths (l.np == 4: dirs 0, 1, 6, 7, four slices per volume set) the same
+// schemes run with paths3 (dirs 0, 6, 7) / paths4 in place of paths7 / paths8.
 // With a median the WTA of a group writes each frame's raw disparity to its own scratch image
 // (post filters read it), so no frame's output is overwritten before its median.
 // With h->rect_on, dLs / dRs are raw images (stride = raw stride) rectified inside the census
@@ -726,7 +732,8 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     const bool up = l.up_wta;
     const int ng = (n + G - 1) / G;
     const uint32_t* items;
-    const int n_items = path_items(h, l, g, 0xFFu, G, st, &items, up ? G : 0);
+    const int np = l.np;           // paths summed: 8, or 4 (dirs 0, 1, 6, 7; the names below follow it)
+    const int n_items = path_items(h, l, g, sgm::census_dir_mask(np), G, st, &items, up ? G : 0);
     if (n_items < 0) return n_items;
     StageRec rec{h};
     if (h->profiling) h->prof_frames += n;
@@ -735,6 +742,7 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     auto path_frames = [&](int k) {
         sgm::PathFrames pf{};
         pf.n = frames_of(k);
+        pf.np = np;
         for (int f = 0; f < pf.n; f++) {
             pf.cL[f] = (const uint64_t*)(ws + l.cL[code_set(k, f)]);
             pf.cR[f] = (const uint64_t*)(ws + l.cR[code_set(k, f)]);
@@ -804,10 +812,14 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
             const sgm::CensusFrames cf = k + 1 < ng ? census_frames(k + 1) : sgm::CensusFrames{};
             // stage name and algorithmic bytes (the canonical dataflow: the dir-1 volume of an
             // up+WTA frame counted as written and read, as if it existed) from the launch's parts
-            const char* name = last ? (wf.n ? "paths8+up_wta" : "paths8")
-                                    : (wf.n ? (cf.n ? "paths7+up_wta+census" : "paths7+up_wta")
-                                            : (cf.n ? "paths7+census" : "paths7"));
-            rec.begin(name, (last ? 8 : 7) * cells * pf.n + (9 * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
+            const char* name8 = last ? (wf.n ? "paths8+up_wta" : "paths8")
+                                     : (wf.n ? (cf.n ? "paths7+up_wta+census" : "paths7+up_wta")
+                                             : (cf.n ? "paths7+census" : "paths7"));
+            const char* name4 = last ? (wf.n ? "paths4+up_wta" : "paths4")
+                                     : (wf.n ? (cf.n ? "paths3+up_wta+census" : "paths3+up_wta")
+                                             : (cf.n ? "paths3+census" : "paths3"));
+            rec.begin(np == 4 ? name4 : name8,
+                      (last ? np : np - 1) * cells * pf.n + ((np + 1) * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
             HIP_TRY(sgm::launch_census_fused(pf, wf, cf, l.vol_bytes, g, items, n_items, dst_stride, true, st),
                     "fused");
             if (wf.n) {
@@ -815,16 +827,18 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
                 HIP_TRY(sgm::launch_census_rowfin(wf, g, dst_stride, st), "rowfin");
             }
         } else if (k == ng) {
-            rec.begin("wta_lr", (8 * cells + 2 * WH) * frames_of(k - 1));
-            HIP_TRY(sgm::launch_census_wta(wta_frames(k - 1), l.vol_bytes, g, dst_stride, st), "wta");
+            rec.begin("wta_lr", (np * cells + 2 * WH) * frames_of(k - 1));
+            HIP_TRY(sgm::launch_census_wta(wta_frames(k - 1), l.vol_bytes, g, dst_stride, st, np), "wta");
         } else if (ng == 1) {
-            rec.begin("paths8", 8 * cells * frames_of(0));
+            rec.begin(np == 4 ? "paths4" : "paths8", np * cells * frames_of(0));
             HIP_TRY(sgm::launch_census_paths(path_frames(0), l.vol_bytes, g, items, n_items, st), "paths");
         } else {
             const sgm::WtaFrames wf = k > 0 ? wta_frames(k - 1) : sgm::WtaFrames{};
             const sgm::CensusFrames cf = k + 1 < ng ? census_frames(k + 1) : sgm::CensusFrames{};
-            const char* name = wf.n ? (cf.n ? "paths8+wta_lr+census" : "paths8+wta_lr") : "paths8+census";
-            rec.begin(name, 8 * cells * frames_of(k) + (8 * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
+            const char* name8 = wf.n ? (cf.n ? "paths8+wta_lr+census" : "paths8+wta_lr") : "paths8+census";
+            const char* name4 = wf.n ? (cf.n ? "paths4+wta_lr+census" : "paths4+wta_lr") : "paths4+census";
+            rec.begin(np == 4 ? name4 : name8,
+                      np * cells * frames_of(k) + (np * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
             HIP_TRY(sgm::launch_census_fused(path_frames(k), wf, cf, l.vol_bytes, g, items, n_items, dst_stride, false,
                                              st),
                     "fused");
@@ -846,8 +860,11 @@ int prepare(sgm_handle* h, int W, int H, bool host_io, Geom& g, Layout& l, int g
 {
     int rc = make_geom(h->params, W, H, g, h->err, &h->bm);
     if (rc) return rc;
+    if (h->params.mode == SGM_MODE_CENSUS8 && h->census_paths != 4 && h->census_paths != 8)
+        return fail(h, SGM_ERR_PARAM, "census paths must be 4 or 8 (sgm_set_census_paths), got " +
+                                          std::to_string(h->census_paths));
     if ((rc = ensure_stream(h))) return rc;
-    l = make_layout(h->params, g, host_io, group, h->n_cu);
+    l = make_layout(h->params, g, host_io, group, h->n_cu, h->census_paths);
     // the uploaded path work list lives in the workspace: any other use of it invalidates it
     if (h->params.mode != SGM_MODE_CENSUS8) { h->items_key[0].clear(); h->items_key[1].clear(); }
     return ensure_ws(h, l.total);
@@ -887,6 +904,7 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
         if (!q && sgm_create(&q, h->device) != SGM_OK) break;
         q->params = h->params;
         q->bm = h->bm;
+        q->census_paths = h->census_paths;
         Geom gq;
         Layout lq;
         if (prepare(q, W, H, false, gq, lq) != SGM_OK) {   // e.g. an allocation failure: fewer lanes
@@ -1054,6 +1072,21 @@ int sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p)
 {
     if (!h || !p) return SGM_ERR_ARG;
     *p = h->bm;
+    return SGM_OK;
+}
+
+int sgm_set_census_paths(sgm_handle* h, int paths)
+{
+    if (!h) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->census_paths = paths;      // checked at match time (prepare), like every parameter
+    return SGM_OK;
+}
+
+int sgm_get_census_paths(const sgm_handle* h, int* paths)
+{
+    if (!h || !paths) return SGM_ERR_ARG;
+    *paths = h->census_paths;
     return SGM_OK;
 }
 
@@ -1420,6 +1453,7 @@ static int open_subs(sgm_handle* h, const int* devices, int n_dev, std::vector<i
         }
         h->sub[i]->params = h->params;
         h->sub[i]->bm = h->bm;
+        h->sub[i]->census_paths = h->census_paths;
     }
     return SGM_OK;
 }
@@ -1989,6 +2023,9 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
     int rc = make_geom(p, W, H, gf, h->err);
     if (rc) return rc;
     if (p.mode != SGM_MODE_CENSUS8) return fail(h, SGM_ERR_UNSUPPORTED, "the exact tile mode runs in the census mode");
+    // the seam exchange carries three directions per sweep family (bnd_slot_of): 8 paths only
+    if (h->census_paths != 8)
+        return fail(h, SGM_ERR_UNSUPPORTED, "the exact tile mode runs with 8 census paths (sgm_set_census_paths)");
     const int nb = n_bands;
     while ((int)h->bands.size() < nb) h->bands.push_back(nullptr);
     std::vector<int> c(nb + 1);
@@ -2306,7 +2343,11 @@ int sgm_debug_census_path(sgm_handle* h, const uint8_t* L, const uint8_t* R, int
     if (h->params.mode != SGM_MODE_CENSUS8) return fail(h, SGM_ERR_PARAM, "census mode required");
     Geom g;
     Layout l;
+    // one direction, not a path set: always the eight-slice layout (slice = direction)
+    const int paths = h->census_paths;
+    h->census_paths = 8;
     int rc = prepare(h, W, H, true, g, l);
+    h->census_paths = paths;
     if (rc || (rc = order_after_last(h, h->stream))) return rc;
     if (g.width1 <= 0) return SGM_OK;
     char* ws = (char*)h->ws.base;

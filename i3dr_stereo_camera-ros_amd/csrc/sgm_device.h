@@ -132,6 +132,13 @@ __host__ __device__ constexpr int vol_d_byte(int g, int k)
 __host__ __device__ constexpr int dir_rx(int i) { return i == 2 || i == 4 || i == 6 ? 1 : (i == 3 || i == 5 || i == 7 ? -1 : 0); }
 __host__ __device__ constexpr int dir_ry(int i) { return i == 0 || i == 2 || i == 3 ? 1 : (i == 1 || i == 4 || i == 5 ? -1 : 0); }
 
+// Census path sets (sgm_set_census_paths). 8: every direction, volume slice = direction.
+// 4: the axis directions {0 down, 1 up, 6, 7}, work-list mask kCensusMask4, in compact slices
+// 0, 1, 2, 3 (a volume set is then four slices long).
+constexpr unsigned kCensusMask4 = 0xC3u;
+__host__ __device__ constexpr unsigned census_dir_mask(int np) { return np == 4 ? kCensusMask4 : 0xFFu; }
+__host__ __device__ constexpr int vol_slot(int np, int dir) { return np == 4 && dir >= 6 ? dir - 4 : dir; }
+
 // lane i <- lane i-1 (lane 0 <- old)
 __device__ __forceinline__ int dpp_shr1(int v, int old) {
     return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xf, 0xf, false);
@@ -321,6 +328,7 @@ struct PathFrames {
     uint8_t* vols[kMaxGroup];
     int n;
     unsigned skip_dirs;     // work-list directions this launch skips (bit d: direction d)
+    int np;                 // path set of the volume sets (vol_slot): 4, or 8 / 0 for all eight
 };
 struct WtaFrames {
     const uint8_t* vols[kMaxGroup];

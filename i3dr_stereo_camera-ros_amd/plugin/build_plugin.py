@@ -1,5 +1,5 @@
 """Build the OpenCV-free plugin core (hip_sgm_core.cpp) into lib/libsgm_plugin_core.so and
-its C++ test drivers lib/plugin_core_test and lib/plugin_bm_test, all linked against lib/libsgm_hip.so with g++.
+its C++ test drivers lib/plugin_core_test, lib/plugin_bm_test and lib/plugin_paths_test, all linked against lib/libsgm_hip.so with g++.
 (matcherHIPSGM.cpp needs OpenCV + the reference headers and is built inside the ROS tree.)"""
 import os
 import subprocess
@@ -34,6 +34,11 @@ def build():
     if _stale(bm_drv, deps + [bm_src]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
                               [bm_src, core_src, "-o", bm_drv] + link)
+    paths_src = os.path.join(HERE, "plugin_paths_test.cpp")
+    paths_drv = os.path.join(LIBDIR, "plugin_paths_test")
+    if _stale(paths_drv, deps + [paths_src]):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
+                              [paths_src, core_src, "-o", paths_drv] + link)
     return so
 
 

@@ -37,8 +37,32 @@ int ocv_compat_from_env(int fallback)
     return (int)bits & (SGM_OCV_COL0_LEGACY | SGM_OCV_SIMD_SAT | SGM_OCV_LANE_TIE);
 }
 
+// SGM_HIP_CENSUS_PATHS = 4 | 8: the census mode's path set (sgm_set_census_paths); unset or
+// blank: `fallback`. Surrounding blanks are ignored; any integer is passed on (a value other
+// than 4 or 8 fails at match time, like every parameter), an unparseable value warns on stderr
+// and keeps the fallback (the Python mirror's census_paths_from_env does the same).
+int census_paths_from_env(int fallback)
+{
+    const char* e = std::getenv("SGM_HIP_CENSUS_PATHS");
+    if (!e) return fallback;
+    std::string v(e);
+    while (!v.empty() && std::isspace((unsigned char)v.back())) v.pop_back();
+    size_t b = 0;
+    while (b < v.size() && std::isspace((unsigned char)v[b])) b++;
+    v = v.substr(b);
+    if (v.empty()) return fallback;
+    char* end = nullptr;
+    const long n = std::strtol(v.c_str(), &end, 10);
+    if (end == v.c_str() || *end || n < -1000000 || n > 1000000) {
+        std::cerr << "SGM_HIP_CENSUS_PATHS=\"" << e << "\" is not 4 or 8: using " << fallback << std::endl;
+        return fallback;
+    }
+    return (int)n;
+}
+
 MatcherCore::MatcherCore(int device, int mode) : device_(device)
 {
+    census_paths_ = census_paths_from_env(8);
     if (mode < 0) {
         const char* env = std::getenv("SGM_HIP_MODE");
         mode = env ? std::atoi(env) : SGM_MODE_OCV_SGBM5;
@@ -104,6 +128,7 @@ void MatcherCore::setP2(float p2) { params_.p2 = (int)p2; }
 void MatcherCore::setInterpolation(bool e) { interpolate_ = e; }
 void MatcherCore::setMode(int m) { params_.mode = m; }
 void MatcherCore::setOcvCompat(int bits) { params_.ocv_compat = bits; }
+void MatcherCore::setCensusPaths(int paths) { census_paths_ = paths; }
 void MatcherCore::setTextureThreshold(int t) { bm_.texture_threshold = t; }
 void MatcherCore::setPreFilterSize(int s) { bm_.prefilter_size = s; }
 
@@ -137,6 +162,7 @@ int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t
     if (!handle_) rc = sgm_create(&handle_, device_);
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
     if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
+    if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
     if (rc == SGM_OK && keep_reg_ && outf) {
         const size_t bytes = out_stride * sizeof(float) * (size_t)(h - 1) + (size_t)w * sizeof(float);
         if (reg_ptr_ != (void*)outf || reg_bytes_ != bytes) {

@@ -18,6 +18,8 @@ namespace sgm_hip {
 
 // SGM_HIP_OCV_COMPAT (melodic | noetic | scalar | <bits>), else `fallback`
 int ocv_compat_from_env(int fallback);
+// SGM_HIP_CENSUS_PATHS (4 | 8, any integer is passed on), else `fallback`
+int census_paths_from_env(int fallback);
 
 class MatcherCore {
 public:
@@ -43,6 +45,9 @@ public:
     void setInterpolation(bool enable);
     void setMode(int mode);
     void setOcvCompat(int bits);   // SGM_OCV_* (default: SGM_HIP_OCV_COMPAT env, else melodic)
+    // SGM_MODE_CENSUS8 only: 8 or 4 aggregation paths (sgm_set_census_paths; default: the
+    // SGM_HIP_CENSUS_PATHS env var, else 8). Forward and backward matches both use it.
+    void setCensusPaths(int paths);
     // cv::StereoBM only (SGM_MODE_OCV_BM); stored but unused in the other modes, where the
     // reference's matchers ignore them too (matcherOpenCVSGBM.h:31-34)
     void setTextureThreshold(int threshold);
@@ -71,6 +76,7 @@ public:
     const sgm_bm_params& bmParams() const { return bm_; }
     bool interpolation() const { return interpolate_; }
     int disparityRange() const { return params_.num_disparities; }
+    int censusPaths() const { return census_paths_; }
     const std::string& lastError() const { return err_; }
     // SGBM modes: cv::ximgproc::createRightMatcher of a StereoSGBM. BM mode: of a StereoBM —
     // minD' = -(minD + D) + 1, same D and window, uniqueness 0, no speckle filter, and (through
@@ -86,6 +92,7 @@ private:
     sgm_handle* handle_ = nullptr;   // opened lazily at the first match
     sgm_params params_{};
     sgm_bm_params bm_{};
+    int census_paths_ = 8;
     bool interpolate_ = false;
     bool keep_reg_ = false;
     void* reg_ptr_ = nullptr;        // the registered output range

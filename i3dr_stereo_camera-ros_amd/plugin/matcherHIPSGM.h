@@ -11,6 +11,7 @@ class MatcherHIPSGM : public AbstractStereoMatcher
 {
 public:
   // mode: an SGM_MODE_* of sgm_hip.h; -1 reads SGM_HIP_MODE (default SGM_MODE_OCV_SGBM5).
+  // The census mode's path set (8 or 4) comes from SGM_HIP_CENSUS_PATHS (hip_sgm_core.h setCensusPaths).
   // SGM_MODE_OCV_BM (3) makes this the drop-in for MatcherOpenCVBlock (cv::StereoBM).
   explicit MatcherHIPSGM(std::string &param_file, cv::Size _image_size, int mode = -1)
       : AbstractStereoMatcher(param_file, _image_size), core_(0, mode)

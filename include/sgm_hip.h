@@ -36,7 +36,10 @@ extern "C" {
  * from 14 to 15 ints (ocv_compat, version 3); round 4 added sgm_match_tiled_device
  * (version 4); version 5 adds SGM_MODE_OCV_BM with the sgm_bm_params entry points. A caller
  * compiled against an older header must check sgm_abi_version() == SGM_ABI_VERSION before
- * passing an sgm_params (a 14-int struct would be read one int past its end).             */
+ * passing an sgm_params (a 14-int struct would be read one int past its end).
+ * sgm_set_census_paths / sgm_get_census_paths were added under version 5: they change no
+ * existing struct or signature (sgm_params stays 15 ints), so the version did not move; a
+ * caller that needs them checks for the symbols.                                          */
 #define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
@@ -149,6 +152,24 @@ void sgm_default_bm_params(sgm_bm_params* p);
 /* The BM-only parameters of a handle (used by SGM_MODE_OCV_BM matches only).                */
 int  sgm_set_bm_params(sgm_handle* h, const sgm_bm_params* p);
 int  sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p);
+
+/* Census mode: the number of aggregation paths, per handle. 8 (the default): all eight
+ * directions. 4: only the axis directions (down, up, left-to-right, right-to-left; directions
+ * 0, 1, 6, 7 of sgm_debug_census_path), S being the u16 sum of those four u8 volumes; each
+ * volume comes from the same recurrence (P1, P2 clamp at 193, path starts) and the WTA,
+ * uniqueness, sub-pixel, LR check, median and speckle steps run unchanged on that S. Four paths
+ * write and read 3 volumes per pipelined frame where eight take 7 and need half the volume
+ * workspace; they trade quality for speed (the diagonals no longer smooth slanted structure).
+ * Like every setter this stores any value: one other than 4 or 8 is SGM_ERR_PARAM at match
+ * time in the census mode. The OCV and BM modes ignore it. Honoured by sgm_match,
+ * sgm_match_f32, sgm_match_device, sgm_match_device_batch[_rect], sgm_match_batch,
+ * sgm_match_tiled and sgm_match_tiled_device (sub-handles inherit it);
+ * sgm_match_tiled_exact runs with 8 paths only (SGM_ERR_UNSUPPORTED with 4: its seam exchange
+ * carries three directions per sweep family; left for later). With 4 paths the profiling
+ * stages are named paths4 / paths3+up_wta.. in place of paths8 / paths7+up_wta.. and
+ * sgm_stage_bytes follows the set (paths4: 4 bytes per cell).                               */
+int  sgm_set_census_paths(sgm_handle* h, int paths);
+int  sgm_get_census_paths(const sgm_handle* h, int* paths);
 
 /* Store parameters. Like the reference's setters this never fails on values; invalid
  * combinations surface at match time (matcherOpenCVSGBM.cpp:37-43 behaviour).            */
@@ -333,7 +354,8 @@ void sgm_cubic_table(int16_t tab[16384]);
 int  sgm_debug_census(sgm_handle* h, const uint8_t* img, int width, int height,
                       size_t stride, uint64_t* out);
 /* Census mode: u8 path-cost volume of direction `dir` (0..7; see DESIGN.md for the order),
- * layout [H][width1][D]. Runs census + that direction only.                               */
+ * layout [H][width1][D]. Runs census + that direction only (a direction, not a path set:
+ * sgm_set_census_paths does not change it).                                                */
 int  sgm_debug_census_path(sgm_handle* h, const uint8_t* left, const uint8_t* right,
                            int width, int height, size_t stride, int dir, uint8_t* vol);
 /* OCV modes: int16 aggregated matching cost C' = SAD + P2 used by the path recurrence,
