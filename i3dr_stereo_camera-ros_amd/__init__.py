@@ -46,6 +46,11 @@ COMPAT_NOETIC = OCV_SIMD_SAT                                    # noetic x86-64 
 COMPAT_MELODIC = OCV_COL0_LEGACY | OCV_SIMD_SAT | OCV_LANE_TIE  # melodic x86-64 (OpenCV 3.2), default
 COMPAT_NAMES = {"scalar": COMPAT_SCALAR, "noetic": COMPAT_NOETIC, "melodic": COMPAT_MELODIC}
 
+# COLOR_BGR2GRAY coefficient sets (include/sgm_hip.h SGM_GRAY_*), over a pixel's bytes in memory order
+GRAY_Y14 = 0   # OpenCV 3.2 (melodic): (c0*1868 + c1*9617 + c2*4899 + 2^13) >> 14
+GRAY_Y15 = 1   # OpenCV 4.x (noetic):  (c0*3735 + c1*19235 + c2*9798 + 2^14) >> 15, unverified against OpenCV
+GRAY_COEFFS = {GRAY_Y14: (1868, 9617, 4899, 14), GRAY_Y15: (3735, 19235, 9798, 15)}
+
 
 def ocv_compat_from_env(default=COMPAT_MELODIC):
     """SGM_HIP_OCV_COMPAT = melodic | noetic | scalar | <bits> (the adapters read the same
@@ -88,6 +93,7 @@ EXPORTS = [
     "sgm_debug_census_path", "sgm_debug_ocv_cost", "sgm_debug_median3", "sgm_debug_speckle", "sgm_debug_path_items",
     "sgm_default_bm_params", "sgm_set_bm_params", "sgm_get_bm_params", "sgm_check_bm_params", "sgm_debug_bm_prefilter",
     "sgm_debug_bm_sad", "sgm_set_census_paths", "sgm_get_census_paths",
+    "sgm_bgr2gray", "sgm_remap_cubic_c3", "sgm_set_raw_format", "sgm_get_raw_format",
 ]
 
 
@@ -205,6 +211,14 @@ def load_library(path=None):
     L.sgm_check_bm_params.argtypes = [P(SgmParams), P(BmParams), ci, ci]
     L.sgm_set_census_paths.argtypes = [vp, ci]
     L.sgm_get_census_paths.argtypes = [vp, P(ci)]
+    # the colour entry points came under ABI version 5: callers check for the symbols
+    for name in ("sgm_bgr2gray", "sgm_remap_cubic_c3", "sgm_set_raw_format", "sgm_get_raw_format"):
+        if not hasattr(L, name):
+            raise ImportError(f"{path}: {name} is missing: rebuild the library")
+    L.sgm_bgr2gray.argtypes = [vp, vp, sz, ci, ci, vp, sz, ci, vp]
+    L.sgm_remap_cubic_c3.argtypes = [vp, vp, sz, ci, ci, vp, vp, sz, ci, ci, vp, sz, vp]
+    L.sgm_set_raw_format.argtypes = [vp, ci, ci]
+    L.sgm_get_raw_format.argtypes = [vp, P(ci), P(ci)]
     L.sgm_debug_bm_prefilter.argtypes = [vp, vp, ci, ci, sz, vp]
     L.sgm_debug_bm_sad.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
     _lib = L
@@ -319,27 +333,44 @@ class Engine:
         self._check(self.lib.sgm_get_census_paths(self.h, ctypes.byref(n)))
         return n.value
 
-    def match(self, left, right):
+    def set_raw_format(self, channels=1, gray_set=GRAY_Y14):
+        """The frames the match entry points take: 1 channel (8UC1, the default) or 3 (interleaved
+        8UC3, converted on the device with COLOR_BGR2GRAY set `gray_set`; strides in bytes). Stored
+        as given; other values fail at match time."""
+        self._check(self.lib.sgm_set_raw_format(self.h, int(channels), int(gray_set)))
+
+    def get_raw_format(self):
+        c, g = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.sgm_get_raw_format(self.h, ctypes.byref(c), ctypes.byref(g)))
+        return c.value, g.value
+
+    def _host_pair(self, left, right):
+        """Contiguous u8 host frames of a match: H x W, or H x W x 3 once set_raw_format(3, ..) was
+        called. Returns (left, right, h, w, row bytes)."""
         left = np.ascontiguousarray(left, np.uint8)
         right = np.ascontiguousarray(right, np.uint8)
-        if left.shape != right.shape or left.ndim != 2:
-            raise ValueError("left/right must be equal-size 2-D u8 images")
-        h, w = left.shape
+        ch = 3 if self.get_raw_format()[0] == 3 else 1
+        if left.shape != right.shape or left.ndim != (3 if ch == 3 else 2) or (ch == 3 and left.shape[2] != 3):
+            raise ValueError("left/right must be equal-size 2-D u8 images" if ch == 1 else
+                             "left/right must be equal-size H x W x 3 u8 images (set_raw_format: 3 channels)")
+        h, w = left.shape[:2]
+        return left, right, h, w, w * ch
+
+    def match(self, left, right):
+        left, right, h, w, row = self._host_pair(left, right)
         out = np.empty((h, w), np.int16)
-        self._check(self.lib.sgm_match(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(out), w))
+        self._check(self.lib.sgm_match(self.h, _ptr(left), _ptr(right), w, h, row, _ptr(out), w))
         return out
 
     def match_f32(self, left, right, out=None):
         """sgm_match_f32: float32 disparity (x16 fixed point, the CV_32FC1 the node's matcher
         contract returns), converted on the device; `out` (float32 rows) is filled in place."""
-        left = np.ascontiguousarray(left, np.uint8)
-        right = np.ascontiguousarray(right, np.uint8)
-        h, w = left.shape
+        left, right, h, w, row = self._host_pair(left, right)
         if out is None:
             out = np.empty((h, w), np.float32)
         if out.dtype != np.float32 or out.shape != (h, w) or out.strides[1] != 4 or out.strides[0] < 4 * w:
             raise ValueError("out must be a float32 (h, w) row-strided array")
-        self._check(self.lib.sgm_match_f32(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(out), out.strides[0] // 4))
+        self._check(self.lib.sgm_match_f32(self.h, _ptr(left), _ptr(right), w, h, row, _ptr(out), out.strides[0] // 4))
         return out
 
     def match_device(self, d_left, d_right, width, height, stride, d_out, out_stride, stream=None):
@@ -530,13 +561,23 @@ class Engine:
                                              vp(d_map_y), map_stride, vp(stream) if stream else None))
 
     def remap_cubic(self, d_src, src_stride, src_w, src_h, d_map_x, d_map_y, map_stride, width, height, d_dst,
-                    dst_stride, stream=None):
+                    dst_stride, stream=None, channels=1):
         """cv::remap(src, dst, map_x, map_y, INTER_CUBIC, BORDER_CONSTANT) on device buffers
-        (generate_disparity.cpp:383)."""
+        (generate_disparity.cpp:383). channels = 3: src and dst are interleaved 8UC3 (H x W x 3),
+        strides in bytes (sgm_remap_cubic_c3)."""
+        if channels not in (1, 3):
+            raise ValueError("remap_cubic takes 1 or 3 channels")
         vp = ctypes.c_void_p
-        self._check(self.lib.sgm_remap_cubic(self.h, vp(d_src), src_stride, src_w, src_h, vp(d_map_x), vp(d_map_y),
-                                             map_stride, width, height, vp(d_dst), dst_stride,
-                                             vp(stream) if stream else None))
+        fn = self.lib.sgm_remap_cubic_c3 if channels == 3 else self.lib.sgm_remap_cubic
+        self._check(fn(self.h, vp(d_src), src_stride, src_w, src_h, vp(d_map_x), vp(d_map_y), map_stride, width,
+                       height, vp(d_dst), dst_stride, vp(stream) if stream else None))
+
+    def bgr2gray(self, d_src, src_stride, width, height, d_dst, dst_stride, gray_set=GRAY_Y14, stream=None):
+        """cv::cvtColor(COLOR_BGR2GRAY) on device buffers: 8UC3 (stride in bytes) -> 8UC1
+        (generate_disparity.cpp:406-416), coefficient set GRAY_Y14 / GRAY_Y15."""
+        vp = ctypes.c_void_p
+        self._check(self.lib.sgm_bgr2gray(self.h, vp(d_src), src_stride, width, height, vp(d_dst), dst_stride,
+                                          int(gray_set), vp(stream) if stream else None))
 
     def census(self, img):
         img = np.ascontiguousarray(img, np.uint8)
@@ -633,18 +674,19 @@ def rectify(engine, image, K, D, R, P, maps=None):
     on the calibration. Returns (rectified u8 image as numpy, maps)."""
     import torch
     img = torch.as_tensor(np.ascontiguousarray(image, np.uint8)).cuda()
-    h, w = img.shape
+    h, w = img.shape[:2]
+    ch = 3 if img.dim() == 3 else 1
     if maps is None:
         mx = torch.empty((h, w), dtype=torch.float32, device="cuda")
         my = torch.empty((h, w), dtype=torch.float32, device="cuda")
         maps = (mx, my)
-    out = torch.empty((h, w), dtype=torch.uint8, device="cuda")
+    out = torch.empty(tuple(img.shape), dtype=torch.uint8, device="cuda")
     stream = _side_stream(torch)
     if len(maps) == 2:
         engine.rectify_map(K, D, R, P, w, h, maps[0].data_ptr(), maps[1].data_ptr(), w, stream.cuda_stream)
         maps = (maps[0], maps[1], True)
-    engine.remap_cubic(img.data_ptr(), w, w, h, maps[0].data_ptr(), maps[1].data_ptr(), w, w, h, out.data_ptr(), w,
-                       stream.cuda_stream)
+    engine.remap_cubic(img.data_ptr(), w * ch, w, h, maps[0].data_ptr(), maps[1].data_ptr(), w, w, h, out.data_ptr(),
+                       w * ch, stream.cuda_stream, channels=ch)
     stream.synchronize()
     return out.cpu().numpy(), maps
 
@@ -753,6 +795,7 @@ class MatcherHIPSGM:
             sys.stderr.write("Images MUST be the same resolution\n")
             return
         # scale 1 (the node always passes 1): cv::resize short-circuits to a copy
+        # H x W x 3 frames are kept as they are: the engine converts them on the device (_run)
         self.left = np.array(left, copy=True)
         self.right = np.array(right, copy=True)
         self.image_size = (self.left.shape[1], self.left.shape[0])
@@ -818,6 +861,10 @@ class MatcherHIPSGM:
         eng = self._engine_for()
         eng.set_params(params)
         eng.set_census_paths(self.census_paths)
+        # colour frames: COLOR_BGR2GRAY on the device, with the grey set of the OpenCV release the
+        # compat bits name (COL0_LEGACY marks 3.x: Y14; otherwise 4.x: Y15)
+        eng.set_raw_format(3 if np.ndim(a) == 3 else 1,
+                           GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm if bm is not None else self.bm_params)
         return eng.match_f32(a, b) if f32 else eng.match(a, b)
@@ -908,13 +955,16 @@ def parameter_callback(config, state):
     return config
 
 
-def bgr2gray(img):
-    """cv::cvtColor(COLOR_BGR2GRAY) for 8U: fixed-point 14-bit coefficients, round half up."""
+def bgr2gray(img, gray_set=GRAY_Y14):
+    """cv::cvtColor(COLOR_BGR2GRAY) for 8U on the host: fixed-point coefficients over the bytes in
+    memory order, round half up. GRAY_Y14 (the default): OpenCV 3.x's 14-bit set; GRAY_Y15: 4.x's
+    15-bit set. `Engine.bgr2gray` is the device form."""
     img = np.asarray(img)
     if img.ndim == 2:
         return img.astype(np.uint8, copy=True)
+    k0, k1, k2, bits = GRAY_COEFFS[gray_set]
     b, g, r = (img[..., i].astype(np.int32) for i in range(3))
-    return ((b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14).astype(np.uint8)
+    return ((b * k0 + g * k1 + r * k2 + (1 << (bits - 1))) >> bits).astype(np.uint8)
 
 
 def stereo_match(matcher, left_mono, right_mono):
@@ -928,10 +978,16 @@ def stereo_match(matcher, left_mono, right_mono):
     return np.empty((0, 0), np.float32)
 
 
-def process_disparity(matcher, left_rect, right_rect, f, T, depth_min=0.0, depth_max=10.0):
+def process_disparity(matcher, left_rect, right_rect, f, T, depth_min=0.0, depth_max=10.0, gray_on_device=False):
     """processDisparity() — generate_disparity.cpp:398-456. Returns the DisparityImage fields
-    or None when the match failed (the node returns -1 and publishes nothing)."""
-    disp = stereo_match(matcher, bgr2gray(left_rect), bgr2gray(right_rect))
+    or None when the match failed (the node returns -1 and publishes nothing).
+    gray_on_device: colour images go to the matcher as they are and the engine converts them
+    (MatcherHIPSGM.setImages: GRAY_Y14 for a 3.x compat setting, GRAY_Y15 otherwise); the default
+    keeps the host bgr2gray(), which is GRAY_Y14 whatever the matcher's compat bits."""
+    if gray_on_device:
+        disp = stereo_match(matcher, left_rect, right_rect)
+    else:
+        disp = stereo_match(matcher, bgr2gray(left_rect), bgr2gray(right_rect))
     if disp.size == 0:
         return None
     dmat = (disp.astype(np.float32) * np.float32(1.0 / 16)).astype(np.float32)

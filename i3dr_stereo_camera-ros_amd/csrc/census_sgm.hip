@@ -112,18 +112,29 @@ __device__ __forceinline__ uint64_t census_code_lds(const uint8_t* tile, int ty,
 
 // 9x7 census: one thread per pixel, a 10 x 72 byte LDS tile per 64 x 4 pixel block.
 // blockIdx.z selects the image (0 = left, 1 = right).
+// ch == 3: the images are interleaved 8UC3 (stride in bytes) and a tile byte is gray(pixel)
+// with the coefficient set `gray` (sgm_set_raw_format).
 __global__ __launch_bounds__(256) void k_census9x7(const uint8_t* __restrict__ L, const uint8_t* __restrict__ R,
                                                    size_t stride, int W, int H,
-                                                   uint64_t* __restrict__ cL, uint64_t* __restrict__ cR)
+                                                   uint64_t* __restrict__ cL, uint64_t* __restrict__ cR, int ch, int gray)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile[10 * 72];
     const uint8_t* img = blockIdx.z ? R : L;
     uint64_t* out = blockIdx.z ? cR : cL;
     const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 4;
-    for (int i = threadIdx.x; i < 10 * 72; i += 256) {
-        int ty = i / 72, tx = i - ty * 72;
-        int yy = min(max(y0 + ty - 3, 0), H - 1), xx = min(max(x0 + tx - 4, 0), W - 1);
-        tile[i] = img[(size_t)yy * stride + xx];
+    if (ch == 3) {
+        for (int i = threadIdx.x; i < 10 * 72; i += 256) {
+            int ty = i / 72, tx = i - ty * 72;
+            int yy = min(max(y0 + ty - 3, 0), H - 1), xx = min(max(x0 + tx - 4, 0), W - 1);
+            const uint8_t* s = img + (size_t)yy * stride + 3 * xx;
+            tile[i] = (uint8_t)gray_px(s[0], s[1], s[2], gray);
+        }
+    } else {
+        for (int i = threadIdx.x; i < 10 * 72; i += 256) {
+            int ty = i / 72, tx = i - ty * 72;
+            int yy = min(max(y0 + ty - 3, 0), H - 1), xx = min(max(x0 + tx - 4, 0), W - 1);
+            tile[i] = img[(size_t)yy * stride + xx];
+        }
     }
     __syncthreads();
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -1037,7 +1048,34 @@ __device__ __forceinline__ void census_block(const CensusFrames& cf, int W, int 
     uint64_t* out = (img & 1) ? pick4(cf.cR, f) : pick4(cf.cL, f);
     const int x0 = (r - by * bx) * 64, y0 = by * kCensusRows;
     constexpr int TH = kCensusRows + 6;
-    if (cf.rect.tab) {      // rectify on the fly: tile = remap(raw) at the clamped positions
+    if (cf.ch == 3) {       // colour frames (uniform: a kernel argument): tile = gray(pixel)
+        if (cf.rect.tab) {  // the node's order: remap the colour image, then convert
+            const float* mx = (img & 1) ? cf.rect.map[2] : cf.rect.map[0];
+            const float* my = (img & 1) ? cf.rect.map[3] : cf.rect.map[1];
+            uint8_t* rect = (img & 1) ? pick4(cf.rectR, f) : pick4(cf.rectL, f);
+            for (int i = threadIdx.x; i < TH * 72; i += kWG) {
+                const int ty = i / 72, tx = i - ty * 72;
+                const int yy = min(max(y0 + ty - 3, 0), H - 1), xx = min(max(x0 + tx - 4, 0), W - 1);
+                const size_t m = (size_t)yy * cf.rect.map_stride + xx;
+                const uint32_t v = remap_cubic_px3(src, cf.stride, cf.rect.src_w, cf.rect.src_h, mx[m], my[m], cf.rect.tab);
+                tile[i] = (uint8_t)gray_px(v & 255, (v >> 8) & 255, v >> 16, cf.gray);
+                // each rectified pixel (3 B) is written by the one block whose interior holds it
+                if (rect && ty >= 3 && ty < 3 + kCensusRows && tx >= 4 && tx < 68 && y0 + ty - 3 < H && x0 + tx - 4 < W) {
+                    uint8_t* d = rect + (size_t)yy * cf.rect_stride + 3 * xx;
+                    d[0] = (uint8_t)v;
+                    d[1] = (uint8_t)(v >> 8);
+                    d[2] = (uint8_t)(v >> 16);
+                }
+            }
+        } else {
+            for (int i = threadIdx.x; i < TH * 72; i += kWG) {
+                const int ty = i / 72, tx = i - ty * 72;
+                const int yy = min(max(y0 + ty - 3, 0), H - 1), xx = min(max(x0 + tx - 4, 0), W - 1);
+                const uint8_t* s = src + (size_t)yy * cf.stride + 3 * xx;
+                tile[i] = (uint8_t)gray_px(s[0], s[1], s[2], cf.gray);
+            }
+        }
+    } else if (cf.rect.tab) {      // rectify on the fly: tile = remap(raw) at the clamped positions
         // (selects, not a dynamic index: that would copy the kernel argument to scratch)
         const float* mx = (img & 1) ? cf.rect.map[2] : cf.rect.map[0];
         const float* my = (img & 1) ? cf.rect.map[3] : cf.rect.map[1];
@@ -1149,10 +1187,10 @@ __global__ __launch_bounds__(kWG) void k_census_rowfin(WtaFrames wf, Geom g, siz
 // host-side launchers
 // ------------------------------------------------------------------------------------
 hipError_t launch_census(const uint8_t* L, const uint8_t* R, size_t stride, int W, int H, uint64_t* cL,
-                         uint64_t* cR, hipStream_t st)
+                         uint64_t* cR, hipStream_t st, int ch, int gray)
 {
     dim3 grid((W + 63) / 64, (H + 3) / 4, R ? 2 : 1);
-    hipLaunchKernelGGL(k_census9x7, grid, dim3(256), 0, st, L, R, stride, W, H, cL, cR);
+    hipLaunchKernelGGL(k_census9x7, grid, dim3(256), 0, st, L, R, stride, W, H, cL, cR, ch, gray);
     return hipGetLastError();
 }
 

@@ -15,6 +15,12 @@
 //                  of the 32 x 32 sub-pixel table (cubic_table, built on the host exactly as
 //                  initInterTab2D builds it); taps outside the image read 0 (BORDER_CONSTANT);
 //                  dst = sat_u8((sum + 2^14) >> 15).
+//  k_remap_cubic_c3 the same for interleaved 8UC3 (the node rectifies colour frames as they
+//                  arrive, generate_disparity.cpp:651-652): channels are independent in OpenCV's
+//                  remapBicubic, so one map look-up and weight row serve three accumulators.
+//  k_bgr2gray      cv::cvtColor(COLOR_BGR2GRAY) 8UC3 -> 8UC1 (generate_disparity.cpp:406-416) in
+//                  its 14-bit (OpenCV 3.x) or 15-bit (4.x) coefficients, over the bytes in memory
+//                  order; restated, unverified against OpenCV.
 //
 // FMA contraction is off for this file: the double map and the float cubic coefficients
 // are bit-identical to the scalar C++ evaluation (oracle/sgm_oracle.py rectify_map /
@@ -77,6 +83,48 @@ __global__ __launch_bounds__(256) void k_remap_cubic(const uint8_t* __restrict__
     if (x >= W || y >= H) return;
     const size_t m = (size_t)y * mstride + x;
     dst[(size_t)y * dstride + x] = remap_cubic_px(src, sstride, sw, sh, mx[m], my[m], tab);
+}
+
+// The same for interleaved 8UC3 (strides in bytes): the map and the weight row of a pixel are
+// read once for its three channels (remap_cubic_px3); 3 B out per pixel as byte stores.
+__global__ __launch_bounds__(256) void k_remap_cubic_c3(const uint8_t* __restrict__ src, size_t sstride, int sw, int sh,
+                                                        const float* __restrict__ mx, const float* __restrict__ my,
+                                                        size_t mstride, int W, int H, const int16_t* __restrict__ tab,
+                                                        uint8_t* __restrict__ dst, size_t dstride)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t m = (size_t)y * mstride + x;
+    const uint32_t v = remap_cubic_px3(src, sstride, sw, sh, mx[m], my[m], tab);
+    uint8_t* d = dst + (size_t)y * dstride + 3 * (size_t)x;
+    d[0] = (uint8_t)v;
+    d[1] = (uint8_t)(v >> 8);
+    d[2] = (uint8_t)(v >> 16);
+}
+
+// cv::cvtColor(COLOR_BGR2GRAY), 8UC3 -> 8UC1 (gray_px): a thread converts 4 consecutive pixels
+// of a row, 12 B in as three dwords and 4 B out as one when both row segments are dword-aligned
+// and whole, byte by byte otherwise (odd strides, the row's tail). blockIdx.z selects the image
+// of a pair (the matchers' pre-pass converts left and right in one launch).
+__global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1,
+                                                  size_t sstride, int W, int H, uint8_t* __restrict__ dst0,
+                                                  uint8_t* __restrict__ dst1, size_t dstride, int set)
+{
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const uint8_t* s = (blockIdx.z ? src1 : src0) + (size_t)y * sstride + 3 * (size_t)x;
+    uint8_t* d = (blockIdx.z ? dst1 : dst0) + (size_t)y * dstride + x;
+    if (x + 4 <= W && (((uintptr_t)s | (uintptr_t)d) & 3) == 0) {
+        const uint32_t a = ((const uint32_t*)s)[0], b = ((const uint32_t*)s)[1], c = ((const uint32_t*)s)[2];
+        const uint32_t g0 = gray_px(a & 255, (a >> 8) & 255, (a >> 16) & 255, set);
+        const uint32_t g1 = gray_px(a >> 24, b & 255, (b >> 8) & 255, set);
+        const uint32_t g2 = gray_px((b >> 16) & 255, b >> 24, c & 255, set);
+        const uint32_t g3 = gray_px((c >> 8) & 255, (c >> 16) & 255, c >> 24, set);
+        *(uint32_t*)d = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+    } else {
+        const int n = min(4, W - x);
+        for (int i = 0; i < n; i++) d[i] = (uint8_t)gray_px(s[3 * i], s[3 * i + 1], s[3 * i + 2], set);
+    }
 }
 
 // ---- host -------------------------------------------------------------------------------
@@ -173,6 +221,24 @@ hipError_t launch_remap_cubic(const uint8_t* src, size_t sstride, int sw, int sh
 {
     hipLaunchKernelGGL(k_remap_cubic, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, src, sstride, sw, sh, mx, my,
                        mstride, W, H, tab, dst, dstride);
+    return hipGetLastError();
+}
+
+hipError_t launch_remap_cubic_c3(const uint8_t* src, size_t sstride, int sw, int sh, const float* mx, const float* my,
+                                 size_t mstride, int W, int H, const int16_t* tab, uint8_t* dst, size_t dstride,
+                                 hipStream_t st)
+{
+    hipLaunchKernelGGL(k_remap_cubic_c3, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, src, sstride, sw, sh, mx,
+                       my, mstride, W, H, tab, dst, dstride);
+    return hipGetLastError();
+}
+
+// src1 / dst1 null: one image
+hipError_t launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, size_t sstride, int W, int H, uint8_t* dst0,
+                           uint8_t* dst1, size_t dstride, int set, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bgr2gray, dim3((W + 255) / 256, (H + 3) / 4, src1 ? 2 : 1), dim3(256), 0, st, src0, src1,
+                       sstride, W, H, dst0, dst1, dstride, set);
     return hipGetLastError();
 }
 

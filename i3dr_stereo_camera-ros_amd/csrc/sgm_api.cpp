@@ -24,7 +24,8 @@
 #include "sgm_hip.h"
 
 namespace sgm {
-hipError_t launch_census(const uint8_t*, const uint8_t*, size_t, int, int, uint64_t*, uint64_t*, hipStream_t);
+hipError_t launch_census(const uint8_t*, const uint8_t*, size_t, int, int, uint64_t*, uint64_t*, hipStream_t, int ch = 1,
+                         int gray = 0);
 int census_path_items(const Geom&, unsigned, int, int, uint32_t*, int, int up_group = 0);
 int census_vol_group(int D);
 hipError_t launch_census_paths(const PathFrames&, size_t, const Geom&, const uint32_t*, int, hipStream_t,
@@ -34,6 +35,9 @@ hipError_t launch_rectify_map(const double*, const double*, const double*, int, 
                               hipStream_t);
 hipError_t launch_remap_cubic(const uint8_t*, size_t, int, int, const float*, const float*, size_t, int, int,
                               const int16_t*, uint8_t*, size_t, hipStream_t);
+hipError_t launch_remap_cubic_c3(const uint8_t*, size_t, int, int, const float*, const float*, size_t, int, int,
+                                 const int16_t*, uint8_t*, size_t, hipStream_t);
+hipError_t launch_bgr2gray(const uint8_t*, const uint8_t*, size_t, int, int, uint8_t*, uint8_t*, size_t, int, hipStream_t);
 void cubic_table(int16_t*);
 bool rectify_inverse(const double*, const double*, double*);
 hipError_t launch_census_tiles(const CensusFrames&, int, int, hipStream_t);
@@ -213,6 +217,8 @@ struct sgm_handle {
     sgm_params params{};
     sgm_bm_params bm = kBmDefaults;   // SGM_MODE_OCV_BM only
     int census_paths = 8;             // SGM_MODE_CENSUS8 only: 8, or 4 (sgm_set_census_paths)
+    int raw_ch = 1;                   // sgm_set_raw_format: channels of the frames (1, or 3 = 8UC3)
+    int gray_set = SGM_GRAY_Y14;      // ... and the COLOR_BGR2GRAY coefficient set used with 3
     hipStream_t stream = nullptr;
     std::string err;
     std::mutex mu;
@@ -395,6 +401,7 @@ struct Layout {
     size_t planes = 0, bufA = 0, bufB = 0, ovols = 0, ovf = 0;  // ocv
     size_t ores = 0;                                       // ocv: per-pixel results of k_ocv_vwta
     size_t bmL = 0, bmR = 0, bmV = 0;                      // bm: pre-filtered images, HBM column sums
+    size_t grayL = 0, grayR = 0;                           // ocv / bm with colour frames: the grey planes
     sgm::BmPlan bm{};                                      // bm: tiling of the fused kernel
     size_t tmp = 0, lab = 0, cnt = 0;                      // post
     size_t inL = 0, inR = 0, out = 0, outf = 0;            // host-API staging (int16 / float out)
@@ -410,7 +417,8 @@ bool use_up_wta()
     return !e || std::atoi(e) != 0;
 }
 
-Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0, int n_cu = 0, int np = 8)
+Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group = 0, int n_cu = 0, int np = 8,
+                   int ch = 1)
 {
     Layout l;
     l.np = np == 4 ? 4 : 8;
@@ -466,7 +474,8 @@ Layout make_layout(const sgm_params& p, const Geom& g, bool host_io, int group =
     }
     l.tmp = take(WH * 2 * (size_t)std::max(group, 1));   // raw disparity before the median (per frame of a group)
     if (p.speckle_window_size > 0) { l.lab = take(WH * 4); l.cnt = take(WH * 4); }
-    if (host_io) { l.inL = take(WH); l.inR = take(WH); l.out = take(WH * 2); l.outf = take(WH * 4); }
+    if (ch == 3 && p.mode != SGM_MODE_CENSUS8) { l.grayL = take(WH); l.grayR = take(WH); }
+    if (host_io) { l.inL = take(WH * ch); l.inR = take(WH * ch); l.out = take(WH * 2); l.outf = take(WH * 4); }
     l.total = off;
     return l;
 }
@@ -590,6 +599,16 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
     const double cells = (double)std::max(g.width1, 0) * g.H * g.D;
     StageRec rec{h};
     if (h->profiling) h->prof_frames++;
+    const int ch = h->raw_ch == 3 ? 3 : 1;
+    if (ch == 3 && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
+        // colour frames: COLOR_BGR2GRAY of both images into the handle's grey planes, then the
+        // unchanged pipeline on those (the census mode converts inside its tiles instead)
+        uint8_t* GL = (uint8_t*)(ws + l.grayL);
+        uint8_t* GR = (uint8_t*)(ws + l.grayR);
+        rec.begin("gray", 6 * WH + 2 * WH);
+        HIP_TRY(sgm::launch_bgr2gray(dL, dR, stride, g.W, g.H, GL, GR, g.W, h->gray_set, st), "gray");
+        dL = GL; dR = GR; stride = g.W;
+    }
     if (g.width1 <= 0) {
         rec.begin("fill_invalid", 2 * WH);
         HIP_TRY(sgm::launch_fill16(dst, dst_stride, g.W, g.H, g.invalid, st), "fill");
@@ -606,15 +625,15 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
         uint64_t* cL = (uint64_t*)(ws + l.cL[0]);
         uint64_t* cR = (uint64_t*)(ws + l.cR[0]);
         uint8_t* vols = (uint8_t*)(ws + l.vols[0]);
-        rec.begin("census", 2 * WH + 16 * WH);
+        rec.begin("census", 2 * ch * WH + 16 * WH);
         if (copy_r) {
-            HIP_TRY(sgm::launch_census(dL, nullptr, stride, g.W, g.H, cL, nullptr, st), "census L");
+            HIP_TRY(sgm::launch_census(dL, nullptr, stride, g.W, g.H, cL, nullptr, st, ch, h->gray_set), "census L");
             const hipEvent_t r_ready = copy_r();
             if (!r_ready) return SGM_ERR_DEVICE;
             HIP_TRY(hipStreamWaitEvent(st, r_ready, 0), "hipStreamWaitEvent");
-            HIP_TRY(sgm::launch_census(dR, nullptr, stride, g.W, g.H, cR, nullptr, st), "census R");
+            HIP_TRY(sgm::launch_census(dR, nullptr, stride, g.W, g.H, cR, nullptr, st, ch, h->gray_set), "census R");
         } else {
-            HIP_TRY(sgm::launch_census(dL, dR, stride, g.W, g.H, cL, cR, st), "census");
+            HIP_TRY(sgm::launch_census(dL, dR, stride, g.W, g.H, cL, cR, st, ch, h->gray_set), "census");
         }
         const uint32_t* items;
         const int n_items = path_items(h, l, g, sgm::census_dir_mask(l.np), 1, st, &items);
@@ -733,6 +752,10 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     const int ng = (n + G - 1) / G;
     const uint32_t* items;
     const int np = l.np;           // paths summed: 8, or 4 (dirs 0, 1, 6, 7; the names below follow it)
+    const int ch = h->raw_ch == 3 ? 3 : 1;
+    // algorithmic bytes of one frame's census: ch B/px read and 8 B/px of codes written per image,
+    // plus, for colour frames, 3 B/px per rectified image written
+    const double census_bytes = (2 * ch + 16 + (ch == 3 ? 3 * ((rectLs ? 1 : 0) + (rectRs ? 1 : 0)) : 0)) * WH;
     const int n_items = path_items(h, l, g, sgm::census_dir_mask(np), G, st, &items, up ? G : 0);
     if (n_items < 0) return n_items;
     StageRec rec{h};
@@ -770,6 +793,8 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
         cf.n = frames_of(k);
         cf.stride = stride;
         cf.rect_stride = rect_stride;
+        cf.ch = ch;
+        cf.gray = h->gray_set;
         if (h->rect_on) cf.rect = h->rect;
         for (int f = 0; f < cf.n; f++) {
             cf.L[f] = dLs[k * G + f];
@@ -788,13 +813,13 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     int hrc = hk_in(0);
     if (hrc) return hrc;
     if (h->rect_on) {           // remap + census of the first group, one launch
-        rec.begin("rectify+census", (2 * WH + 16 * WH + 16 * WH) * frames_of(0));
+        rec.begin("rectify+census", (census_bytes + 16 * WH) * frames_of(0));
         HIP_TRY(sgm::launch_census_tiles(census_frames(0), g.W, g.H, st), "rectify+census");
     } else {
         for (int f = 0; f < frames_of(0); f++) {
-            rec.begin("census", 2 * WH + 16 * WH);
+            rec.begin("census", census_bytes);
             HIP_TRY(sgm::launch_census(dLs[f], dRs[f], stride, g.W, g.H, (uint64_t*)(ws + l.cL[code_set(0, f)]),
-                                       (uint64_t*)(ws + l.cR[code_set(0, f)]), st), "census");
+                                       (uint64_t*)(ws + l.cR[code_set(0, f)]), st, ch, h->gray_set), "census");
         }
     }
     for (int k = 0; k <= ng; k++) {
@@ -819,7 +844,7 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
                                      : (wf.n ? (cf.n ? "paths3+up_wta+census" : "paths3+up_wta")
                                              : (cf.n ? "paths3+census" : "paths3"));
             rec.begin(np == 4 ? name4 : name8,
-                      (last ? np : np - 1) * cells * pf.n + ((np + 1) * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
+                      (last ? np : np - 1) * cells * pf.n + ((np + 1) * cells + 2 * WH) * wf.n + census_bytes * cf.n);
             HIP_TRY(sgm::launch_census_fused(pf, wf, cf, l.vol_bytes, g, items, n_items, dst_stride, true, st),
                     "fused");
             if (wf.n) {
@@ -838,7 +863,7 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
             const char* name8 = wf.n ? (cf.n ? "paths8+wta_lr+census" : "paths8+wta_lr") : "paths8+census";
             const char* name4 = wf.n ? (cf.n ? "paths4+wta_lr+census" : "paths4+wta_lr") : "paths4+census";
             rec.begin(np == 4 ? name4 : name8,
-                      np * cells * frames_of(k) + (np * cells + 2 * WH) * wf.n + 18 * WH * cf.n);
+                      np * cells * frames_of(k) + (np * cells + 2 * WH) * wf.n + census_bytes * cf.n);
             HIP_TRY(sgm::launch_census_fused(path_frames(k), wf, cf, l.vol_bytes, g, items, n_items, dst_stride, false,
                                              st),
                     "fused");
@@ -856,6 +881,28 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     return SGM_OK;
 }
 
+// sgm_set_raw_format stores anything; a match needs 1 or 3 channels and a known grey set
+int raw_format_status(sgm_handle* h)
+{
+    if (h->raw_ch != 1 && h->raw_ch != 3)
+        return fail(h, SGM_ERR_PARAM, "raw format: channels must be 1 or 3 (sgm_set_raw_format), got " +
+                                          std::to_string(h->raw_ch));
+    if (h->gray_set != SGM_GRAY_Y14 && h->gray_set != SGM_GRAY_Y15)
+        return fail(h, SGM_ERR_PARAM, "raw format: unknown grey set " + std::to_string(h->gray_set));
+    return SGM_OK;
+}
+// the entry points whose sub-handles do not carry the raw format yet
+int refuse_colour(sgm_handle* h, const char* what)
+{
+    const int rc = raw_format_status(h);
+    if (rc) return rc;
+    if (h->raw_ch == 3)
+        return fail(h, SGM_ERR_UNSUPPORTED, std::string(what) + " takes mono frames only (sgm_set_raw_format: 3 channels)");
+    return SGM_OK;
+}
+// bytes per pixel of the frames a match takes
+size_t raw_bpp(const sgm_handle* h) { return h->raw_ch == 3 ? 3 : 1; }
+
 int prepare(sgm_handle* h, int W, int H, bool host_io, Geom& g, Layout& l, int group = 0)
 {
     int rc = make_geom(h->params, W, H, g, h->err, &h->bm);
@@ -863,8 +910,9 @@ int prepare(sgm_handle* h, int W, int H, bool host_io, Geom& g, Layout& l, int g
     if (h->params.mode == SGM_MODE_CENSUS8 && h->census_paths != 4 && h->census_paths != 8)
         return fail(h, SGM_ERR_PARAM, "census paths must be 4 or 8 (sgm_set_census_paths), got " +
                                           std::to_string(h->census_paths));
+    if ((rc = raw_format_status(h))) return rc;
     if ((rc = ensure_stream(h))) return rc;
-    l = make_layout(h->params, g, host_io, group, h->n_cu, h->census_paths);
+    l = make_layout(h->params, g, host_io, group, h->n_cu, h->census_paths, h->raw_ch);
     // the uploaded path work list lives in the workspace: any other use of it invalidates it
     if (h->params.mode != SGM_MODE_CENSUS8) { h->items_key[0].clear(); h->items_key[1].clear(); }
     return ensure_ws(h, l.total);
@@ -905,6 +953,8 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
         q->params = h->params;
         q->bm = h->bm;
         q->census_paths = h->census_paths;
+        q->raw_ch = h->raw_ch;
+        q->gray_set = h->gray_set;
         Geom gq;
         Layout lq;
         if (prepare(q, W, H, false, gq, lq) != SGM_OK) {   // e.g. an allocation failure: fewer lanes
@@ -982,7 +1032,8 @@ int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, 
         HIP_TRY(hipEventRecord(h->cpy_ev, st), "hipEventRecord");        // the workspace is free
         HIP_TRY(hipStreamWaitEvent(h->cpy, h->cpy_ev, 0), "hipStreamWaitEvent");
     }
-    HIP_TRY(hipMemcpy2DAsync(ws + l.inL, W, L, stride, W, H, hipMemcpyHostToDevice, st), "H2D L");
+    const size_t row = (size_t)W * raw_bpp(h);    // bytes of an input row (8UC3 with colour frames)
+    HIP_TRY(hipMemcpy2DAsync(ws + l.inL, row, L, stride, row, H, hipMemcpyHostToDevice, st), "H2D L");
     // f32 output that is the WTA's own (census, no median / speckles) into a registered, mapped
     // host buffer: the WTA writes the float rows there itself (no to-float pass, no copy back)
     float* outf = nullptr;
@@ -998,15 +1049,15 @@ int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, 
     std::function<hipEvent_t()> copy_r;
     if (census) {
         copy_r = [&]() -> hipEvent_t {
-            hipError_t e = hipMemcpy2DAsync(ws + l.inR, W, R, stride, W, H, hipMemcpyHostToDevice, h->cpy);
+            hipError_t e = hipMemcpy2DAsync(ws + l.inR, row, R, stride, row, H, hipMemcpyHostToDevice, h->cpy);
             if (e == hipSuccess) e = hipEventRecord(h->cpy_ev, h->cpy);
             if (e != hipSuccess) { hip_fail(h, e, "H2D R"); return nullptr; }
             return h->cpy_ev;
         };
     } else {
-        HIP_TRY(hipMemcpy2DAsync(ws + l.inR, W, R, stride, W, H, hipMemcpyHostToDevice, st), "H2D R");
+        HIP_TRY(hipMemcpy2DAsync(ws + l.inR, row, R, stride, row, H, hipMemcpyHostToDevice, st), "H2D R");
     }
-    rc = run_pipeline(h, l, g, (const uint8_t*)(ws + l.inL), (const uint8_t*)(ws + l.inR), W, d16, W, copy_r, outf,
+    rc = run_pipeline(h, l, g, (const uint8_t*)(ws + l.inL), (const uint8_t*)(ws + l.inR), row, d16, W, copy_r, outf,
                       out_stride);
     if (rc) return rc;
     if (outf) {
@@ -1087,6 +1138,23 @@ int sgm_get_census_paths(const sgm_handle* h, int* paths)
 {
     if (!h || !paths) return SGM_ERR_ARG;
     *paths = h->census_paths;
+    return SGM_OK;
+}
+
+int sgm_set_raw_format(sgm_handle* h, int channels, int gray_set)
+{
+    if (!h) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->raw_ch = channels;         // checked at match time (prepare), like every parameter
+    h->gray_set = gray_set;
+    return SGM_OK;
+}
+
+int sgm_get_raw_format(const sgm_handle* h, int* channels, int* gray_set)
+{
+    if (!h || !channels || !gray_set) return SGM_ERR_ARG;
+    *channels = h->raw_ch;
+    *gray_set = h->gray_set;
     return SGM_OK;
 }
 
@@ -1220,7 +1288,8 @@ int sgm_match_device(sgm_handle* h, const uint8_t* dL, const uint8_t* dR, int W,
         return sgm_match_device_batch_rect(h, l1, r1, 1, W, H, stride, nullptr, nullptr, 0, o1, out_stride, stream);
     }
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!dL || !dR || !dOut || stride < (size_t)W || out_stride < (size_t)W) return fail(h, SGM_ERR_ARG, "bad buffers");
+    if (!dL || !dR || !dOut || W <= 0 || stride < (size_t)W * raw_bpp(h) || out_stride < (size_t)W)
+        return fail(h, SGM_ERR_ARG, "bad buffers");
     Geom g;
     Layout l;
     int rc = prepare(h, W, H, false, g, l);
@@ -1240,11 +1309,12 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
 {
     if (!h) return SGM_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    const size_t in_w = h->rect_on ? (size_t)h->rect.src_w : (size_t)W;
-    if (n < 0 || (n > 0 && (!dLs || !dRs || !outs)) || stride < in_w || out_stride < (size_t)W)
+    const size_t bpp = raw_bpp(h);     // strides of colour frames are in bytes
+    const size_t in_w = (h->rect_on ? (size_t)h->rect.src_w : (size_t)std::max(W, 0)) * bpp;
+    if (n < 0 || (n > 0 && (!dLs || !dRs || !outs)) || stride < in_w || out_stride < (size_t)std::max(W, 0))
         return fail(h, SGM_ERR_ARG, "bad buffers");
-    if ((rectLs || rectRs) && (!h->rect_on || rect_stride < (size_t)W))
-        return fail(h, SGM_ERR_ARG, "rectified outputs need sgm_set_rectification and rect_stride >= width");
+    if ((rectLs || rectRs) && (!h->rect_on || rect_stride < (size_t)std::max(W, 0) * bpp))
+        return fail(h, SGM_ERR_ARG, "rectified outputs need sgm_set_rectification and rect_stride >= a row's bytes");
     for (int i = 0; i < n; i++)
         if (!dLs[i] || !dRs[i] || !outs[i]) return fail(h, SGM_ERR_ARG, "null frame pointer");
     if (n == 0) return SGM_OK;
@@ -1352,6 +1422,40 @@ int sgm_remap_cubic(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int 
     return SGM_OK;
 }
 
+int sgm_remap_cubic_c3(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int src_w, int src_h,
+                       const float* d_map_x, const float* d_map_y, size_t map_stride, int W, int H, uint8_t* d_dst,
+                       size_t dst_stride, void* stream)
+{
+    if (!h) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!d_src || !d_map_x || !d_map_y || !d_dst || W <= 0 || H <= 0 || src_w <= 0 || src_h <= 0 ||
+        src_stride < (size_t)src_w * 3 || map_stride < (size_t)W || dst_stride < (size_t)W * 3)
+        return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
+    int rc = ensure_stream(h);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = ensure_cubic_table(h))) return rc;
+    HIP_TRY(sgm::launch_remap_cubic_c3(d_src, src_stride, src_w, src_h, d_map_x, d_map_y, map_stride, W, H,
+                                       h->cubic_tab, d_dst, dst_stride, st), "remap_cubic_c3");
+    return SGM_OK;
+}
+
+int sgm_bgr2gray(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int W, int H, uint8_t* d_dst,
+                 size_t dst_stride, int gray_set, void* stream)
+{
+    if (!h) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!d_src || !d_dst || W <= 0 || H <= 0 || src_stride < (size_t)W * 3 || dst_stride < (size_t)W)
+        return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
+    if (gray_set != SGM_GRAY_Y14 && gray_set != SGM_GRAY_Y15)
+        return fail(h, SGM_ERR_PARAM, "unknown grey set " + std::to_string(gray_set));
+    int rc = ensure_stream(h);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    HIP_TRY(sgm::launch_bgr2gray(d_src, nullptr, src_stride, W, H, d_dst, nullptr, dst_stride, gray_set, st), "bgr2gray");
+    return SGM_OK;
+}
+
 void sgm_calc_q(const double K[9], const double Pr[12], const double Pl[12], double Q[16])
 {
     // disparity_to_depth.cpp:62-84
@@ -1414,7 +1518,7 @@ int sgm_match(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, s
     if (!h) return SGM_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification applies to device-buffer matches");
-    if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W)
+    if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W * raw_bpp(h) || out_stride < (size_t)W)
         return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
     return match_host(h, L, R, W, H, stride, disp, out_stride, false);
 }
@@ -1425,7 +1529,7 @@ int sgm_match_f32(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int 
     if (!h) return SGM_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification applies to device-buffer matches");
-    if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W)
+    if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W * raw_bpp(h) || out_stride < (size_t)W)
         return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
     return match_host(h, L, R, W, H, stride, disp, out_stride, true);
 }
@@ -1771,6 +1875,7 @@ int sgm_match_batch(sgm_handle* h, const uint8_t* const* lefts, const uint8_t* c
 {
     if (!h || !lefts || !rights || !disps || n_frames < 0) return SGM_ERR_ARG;
     if (W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W) return fail(h, SGM_ERR_ARG, "bad sizes");
+    if (int rf = refuse_colour(h, "sgm_match_batch")) return rf;
     for (int i = 0; i < n_frames; i++)
         if (!lefts[i] || !rights[i] || !disps[i]) return fail(h, SGM_ERR_ARG, "null frame pointer");
     if (n_frames == 0) return SGM_OK;
@@ -1792,6 +1897,7 @@ int sgm_match_tiled(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
     if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W || n_bands < 1 ||
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
+    if (int rf = refuse_colour(h, "sgm_match_tiled")) return rf;
     n_bands = std::min(n_bands, H);
     std::vector<int> devs;
     int rc = open_subs(h, devices, n_dev, devs);
@@ -1855,6 +1961,7 @@ extern "C" int sgm_match_tiled_device(sgm_handle* h, const uint8_t* dL, const ui
     if (!dL || !dR || !dOut || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W || n_bands < 1 ||
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
+    if (int rf = refuse_colour(h, "sgm_match_tiled_device")) return rf;
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "the tile mode takes rectified images");
     n_bands = std::min(n_bands, H);
     std::vector<int> devs;
@@ -2250,6 +2357,7 @@ int sgm_match_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int
     if (!h) return SGM_ERR_ARG;
     if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W || n_bands < 1)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes or band count");
+    if (int rf = refuse_colour(h, "sgm_match_tiled_exact")) return rf;
     std::vector<int> devs;
     if (!devices || n_dev <= 0) {
         for (int i = 0; i < sgm_device_count(); i++) devs.push_back(i);

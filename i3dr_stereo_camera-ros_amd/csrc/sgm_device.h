@@ -355,7 +355,9 @@ struct RectifyIn {
 };
 // census transforms of the next group, run in the tail of a fused launch. With rect.tab
 // set, L/R are raw images (stride = raw stride) and the rectified pixels are also written
-// to rectL/rectR (when not null).
+// to rectL/rectR (when not null). ch == 3: L/R are interleaved 8UC3 (strides in bytes), the
+// census runs on gray(pixel) resp. gray(remap3(raw)) with the coefficient set `gray`, and
+// rectL/rectR receive the rectified 8UC3 pixels. ch 0 or 1: mono.
 struct CensusFrames {
     const uint8_t* L[kMaxGroup];
     const uint8_t* R[kMaxGroup];
@@ -365,8 +367,17 @@ struct CensusFrames {
     uint8_t* rectR[kMaxGroup];
     size_t stride, rect_stride;
     int n;
+    int ch, gray;                // raw format (sgm_set_raw_format): channels, SGM_GRAY_*
     RectifyIn rect;
 };
+
+// cv::cvtColor(COLOR_BGR2GRAY) of one 8UC3 pixel, bytes in memory order c0, c1, c2
+// (SGM_GRAY_Y14: OpenCV 3.x, 14-bit coefficients; SGM_GRAY_Y15: 4.x, 15-bit; round half up)
+__device__ __forceinline__ int gray_px(int c0, int c1, int c2, int set)
+{
+    return set == SGM_GRAY_Y15 ? (c0 * 3735 + c1 * 19235 + c2 * 9798 + (1 << 14)) >> 15
+                               : (c0 * 1868 + c1 * 9617 + c2 * 4899 + (1 << 13)) >> 14;
+}
 
 // One pixel of cv::remap(src, map_x, map_y, INTER_CUBIC, BORDER_CONSTANT 0) for u8 (rectify.hip)
 __device__ __forceinline__ int remap_round_sat(float v)
@@ -399,6 +410,54 @@ __device__ __forceinline__ uint8_t remap_cubic_px(const uint8_t* __restrict__ sr
         }
     }
     return (uint8_t)min(max((sum + (1 << 14)) >> 15, 0), 255);
+}
+
+// The same for one interleaved 8UC3 pixel (sstride in bytes): OpenCV's remapBicubic treats the
+// channels independently with the same position and weights, so one map look-up and one table
+// row serve three accumulators, and each channel equals remap_cubic_px of its plane. Returns
+// c0 | c1 << 8 | c2 << 16.
+__device__ __forceinline__ uint32_t remap_cubic_px3(const uint8_t* __restrict__ src, size_t sstride, int sw, int sh,
+                                                    float fx, float fy, const int16_t* __restrict__ tab)
+{
+    const int X = remap_round_sat(fx * 32.0f), Y = remap_round_sat(fy * 32.0f);
+    const int sx = min(max(X >> 5, -32768), 32767) - 1, sy = min(max(Y >> 5, -32768), 32767) - 1;
+    const int16_t* w = tab + (size_t)(((Y & 31) * 32 + (X & 31)) * 16);
+    int s0 = 0, s1 = 0, s2 = 0;
+    if ((unsigned)sx < (unsigned)max(sw - 3, 0) && (unsigned)sy < (unsigned)max(sh - 3, 0)) {
+        const uint8_t* s = src + (size_t)sy * sstride + 3 * sx;
+        // one tap row (12 B, 4 weights) in flight at a time: the census kernels this is inlined
+        // into keep their register counts
+#pragma unroll 1
+        for (int k1 = 0; k1 < 4; k1++, s += sstride)
+#pragma unroll
+            for (int k2 = 0; k2 < 4; k2++) {
+                const int wk = (int)w[k1 * 4 + k2];
+                s0 += (int)s[3 * k2] * wk;
+                s1 += (int)s[3 * k2 + 1] * wk;
+                s2 += (int)s[3 * k2 + 2] * wk;
+            }
+    } else {
+#pragma unroll 1
+        for (int k1 = 0; k1 < 4; k1++) {
+            const int yy = sy + k1;
+            if (yy < 0 || yy >= sh) continue;
+#pragma unroll
+            for (int k2 = 0; k2 < 4; k2++) {
+                const int xx = sx + k2;
+                if (xx >= 0 && xx < sw) {
+                    const uint8_t* s = src + (size_t)yy * sstride + 3 * xx;
+                    const int wk = (int)w[k1 * 4 + k2];
+                    s0 += (int)s[0] * wk;
+                    s1 += (int)s[1] * wk;
+                    s2 += (int)s[2] * wk;
+                }
+            }
+        }
+    }
+    const uint32_t v0 = (uint32_t)min(max((s0 + (1 << 14)) >> 15, 0), 255);
+    const uint32_t v1 = (uint32_t)min(max((s1 + (1 << 14)) >> 15, 0), 255);
+    const uint32_t v2 = (uint32_t)min(max((s2 + (1 << 14)) >> 15, 0), 255);
+    return v0 | (v1 << 8) | (v2 << 16);
 }
 
 struct RowLds {

@@ -39,7 +39,8 @@ extern "C" {
  * passing an sgm_params (a 14-int struct would be read one int past its end).
  * sgm_set_census_paths / sgm_get_census_paths were added under version 5: they change no
  * existing struct or signature (sgm_params stays 15 ints), so the version did not move; a
- * caller that needs them checks for the symbols.                                          */
+ * caller that needs them checks for the symbols. The colour entry points (sgm_bgr2gray,
+ * sgm_remap_cubic_c3, sgm_set_raw_format, sgm_get_raw_format) came the same way.          */
 #define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
@@ -171,6 +172,42 @@ int  sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p);
 int  sgm_set_census_paths(sgm_handle* h, int paths);
 int  sgm_get_census_paths(const sgm_handle* h, int* paths);
 
+/* ---- colour frames ---------------------------------------------------------------------- */
+/* The node accepts colour cameras: imageCb rectifies whatever encoding arrives
+ * (generate_disparity.cpp:651-652, :674-675) and processDisparity converts both rectified images
+ * with cv::cvtColor(COLOR_BGR2GRAY) before the matcher (:406-416). The two coefficient sets of
+ * that conversion for 8UC3 -> 8UC1, over the bytes of a pixel in MEMORY order c0, c1, c2:
+ *   SGM_GRAY_Y14  (c0*1868 + c1*9617 + c2*4899 + 2^13) >> 14   OpenCV 3.2 (melodic)
+ *   SGM_GRAY_Y15  (c0*3735 + c1*19235 + c2*9798 + 2^14) >> 15  OpenCV 4.x (noetic)
+ * Both are restatements: Y14 is what the Python mirror's bgr2gray() always did, Y15 is recalled
+ * from OpenCV 4's colour code, and neither is verified against a real OpenCV (like every other
+ * OpenCV restatement here). The node applies COLOR_BGR2GRAY whatever the message encoding, so an
+ * RGB8 frame gets the R and B weights swapped; this API reproduces that: there is no channel-
+ * order flag, callers pass the bytes as the node would see them.                            */
+#define SGM_GRAY_Y14 0
+#define SGM_GRAY_Y15 1
+
+/* The raw format of the frames the match entry points take, per handle: channels 1 (8UC1, the
+ * default) or 3 (interleaved 8UC3), and the grey set used with 3 channels (default
+ * SGM_GRAY_Y14). Like every setter this stores any value: channels other than 1 or 3, or an
+ * unknown grey set, are SGM_ERR_PARAM at match time. With channels = 3:
+ *  - sgm_match, sgm_match_f32, sgm_match_device, sgm_match_device_batch and
+ *    sgm_match_device_batch_rect take 8UC3 frames; their `stride` is in bytes (>= 3 * width).
+ *  - under sgm_set_rectification the frames are raw colour, and the rectified outputs of
+ *    sgm_match_device_batch_rect are rectified 8UC3 (rect_stride in bytes, >= 3 * width): what
+ *    the node publishes and what sgm_depth_points(channels = 3) colours the cloud with.
+ *  - the order is the node's: the colour image is remapped first, then converted; a grey image
+ *    is never remapped. The census mode does both inside its census tiles (no grey image
+ *    exists in memory); the OCV and BM modes convert both images into per-handle grey planes
+ *    first (profiling stage `gray`) and run their pipelines unchanged (they still refuse fused
+ *    rectification: rectify with sgm_remap_cubic_c3, the match converts).
+ *  - sgm_match_batch, sgm_match_tiled, sgm_match_tiled_device and sgm_match_tiled_exact return
+ *    SGM_ERR_UNSUPPORTED (their sub-handles do not carry the format yet).
+ * sgm_stage_bytes of the census stages then counts 3 B/px read per image, plus 3 B/px per
+ * rectified image written.                                                                  */
+int  sgm_set_raw_format(sgm_handle* h, int channels, int gray_set);
+int  sgm_get_raw_format(const sgm_handle* h, int* channels, int* gray_set);
+
 /* Store parameters. Like the reference's setters this never fails on values; invalid
  * combinations surface at match time (matcherOpenCVSGBM.cpp:37-43 behaviour).            */
 int  sgm_set_params(sgm_handle* h, const sgm_params* p);
@@ -183,9 +220,9 @@ int  sgm_check_params(const sgm_params* p, int width, int height);
 int  sgm_check_bm_params(const sgm_params* p, const sgm_bm_params* bm, int width, int height);
 
 /* ---- matching -------------------------------------------------------------------------- */
-/* Host buffers in, host buffer out; synchronous. L/R: W x H u8 mono (stride bytes);
- * disp: W x H int16 (out_stride in elements). Replaces cv::StereoSGBM::compute
- * (matcherOpenCVSGBM.cpp:21).                                                              */
+/* Host buffers in, host buffer out; synchronous. L/R: W x H u8 mono (stride bytes), or 8UC3
+ * after sgm_set_raw_format(h, 3, ..); disp: W x H int16 (out_stride in elements). Replaces
+ * cv::StereoSGBM::compute (matcherOpenCVSGBM.cpp:21).                                      */
 int  sgm_match(sgm_handle* h, const uint8_t* left, const uint8_t* right,
                int width, int height, size_t stride,
                int16_t* disp, size_t out_stride);
@@ -329,6 +366,18 @@ int  sgm_rectify_map(sgm_handle* h, const double K[9], const double* D, int n_di
 int  sgm_remap_cubic(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int src_w, int src_h,
                      const float* d_map_x, const float* d_map_y, size_t map_stride, int width, int height,
                      uint8_t* d_dst, size_t dst_stride, void* stream);
+/* The same for an interleaved 8UC3 image (src_stride, dst_stride in bytes; src and dst are
+ * 8UC3): one map look-up and one weight row per pixel shared by the three channels, each
+ * channel equal to sgm_remap_cubic of its plane (OpenCV's remapBicubic treats channels
+ * independently); taps outside the source read 0 in every channel.                          */
+int  sgm_remap_cubic_c3(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int src_w, int src_h,
+                        const float* d_map_x, const float* d_map_y, size_t map_stride, int width, int height,
+                        uint8_t* d_dst, size_t dst_stride, void* stream);
+/* cv::cvtColor(COLOR_BGR2GRAY) on device buffers: src 8UC3 (src_stride in bytes), dst 8UC1
+ * (dst_stride in bytes), gray_set = SGM_GRAY_Y14 / SGM_GRAY_Y15 (another value: SGM_ERR_PARAM).
+ * Asynchronous on `stream`.                                                                 */
+int  sgm_bgr2gray(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int width, int height,
+                  uint8_t* d_dst, size_t dst_stride, int gray_set, void* stream);
 /* Rectification fused into the census (census mode): after this call the device matches
  * (sgm_match_device, sgm_match_device_batch, sgm_match_device_batch_rect) take RAW images of
  * src_width x src_height (their stride argument = the raw stride) and rectify them inside
