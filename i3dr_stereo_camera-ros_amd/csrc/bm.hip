@@ -22,12 +22,11 @@
 // e = D - 1 - (d - minD): e = 0 is the largest disparity (OpenCV scans in this order and keeps
 // the first minimum, so equal minima resolve to the largest disparity).
 #include "sgm_device.h"
+#include "sgm_launch.h"
 
 #include <cstdlib>
 
 namespace sgm {
-
-hipError_t launch_fill16(int16_t*, size_t, int, int, int, hipStream_t);
 
 constexpr int kBmMaxWaves = 16;
 // waves of a workgroup: 16, or 8 for D > 1024 (32 chunks per lane need more than 128 VGPRs)

@@ -13,6 +13,7 @@
 // The matching cost popcount(cL ^ cR) is recomputed on the fly in every path (never
 // stored); S never touches HBM.
 #include "sgm_device.h"
+#include "sgm_launch.h"
 
 #include <atomic>
 #include <string>
@@ -1197,16 +1198,38 @@ hipError_t launch_census(const uint8_t* L, const uint8_t* R, size_t stride, int 
 static int dpl16_for(int D) { return D <= 32 ? 2 : D <= 64 ? 4 : D <= 128 ? 8 : D <= 256 ? 16 : 32; }
 // chunk size of the volumes' interleaved byte order for a search of D disparities (pair_group)
 int census_vol_group(int D) { return pair_group(dpl16_for(D)); }
+
+// The template arguments of a census launch from its runtime values, the one place that maps
+// them: calls f(dpl, exact, np) with integral constants — dpl = disparities per lane for D
+// (2 .. 32), exact = D fills the 16 lanes of a line (D == 16 * dpl), np = 4 or 8 paths.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <typename F>
+static void with_launch_consts(int D, int np, F&& f)
+{
+    auto with_dpl = [&](auto dpl) {
+        auto with_exact = [&](auto exact) {
+            if (np == 4) f(dpl, exact, IntC<4>{});
+            else f(dpl, exact, IntC<8>{});
+        };
+        if (D == 16 * decltype(dpl)::value) with_exact(std::true_type{});
+        else with_exact(std::false_type{});
+    };
+    switch (dpl16_for(D)) {
+    case 2: with_dpl(IntC<2>{}); break;
+    case 4: with_dpl(IntC<4>{}); break;
+    case 8: with_dpl(IntC<8>{}); break;
+    case 16: with_dpl(IntC<16>{}); break;
+    default: with_dpl(IntC<32>{}); break;
+    }
+}
+
 // lines per row-sweep workgroup (RowsCfg<DPL>::NL of the launch's DPL)
 static int rows_lines(int D)
 {
-    switch (dpl16_for(D)) {
-    case 2: return RowsCfg<2>::NL;
-    case 4: return RowsCfg<4>::NL;
-    case 8: return RowsCfg<8>::NL;
-    case 16: return RowsCfg<16>::NL;
-    default: return RowsCfg<32>::NL;
-    }
+    int nl = 0;
+    with_launch_consts(D, 8, [&](auto dpl, auto, auto) { nl = RowsCfg<decltype(dpl)::value>::NL; });
+    return nl;
 }
 // image rows per horizontal-scan workgroup (LineCfg<DPL>::HROWS of the launch's DPL)
 static int hscan_rows(int D) { return dpl16_for(D) == 32 ? LineCfg<32>::HROWS : LineCfg<16>::HROWS; }
@@ -1308,21 +1331,6 @@ static void trace_dump(uint64_t* tr, int n_blocks, hipStream_t st)
     }
 }
 
-template <int DPL>
-static void launch_paths_dpl(const PathFrames& pf, size_t vol_bytes, size_t trash_off, const Geom& g,
-                             const PathLaunch16& pl, const uint32_t* items, int n_items, hipStream_t st)
-{
-    uint64_t* tr = trace_buffer(n_items);
-    dim3 grid(n_items), block(kWG);
-    if (g.D == 16 * DPL)
-        hipLaunchKernelGGL((k_census_paths16<DPL, true>), grid, block, 0, st, pf, vol_bytes, trash_off, g, pl, items,
-                           tr);
-    else
-        hipLaunchKernelGGL((k_census_paths16<DPL, false>), grid, block, 0, st, pf, vol_bytes, trash_off, g, pl, items,
-                           tr);
-    trace_dump(tr, n_items, st);
-}
-
 // Path sweeps of the frames in pf (codes -> volumes). Each volume slice is vol_bytes long:
 // H*width1*D cells followed by a trash slot. items: device copy of census_path_items().
 // bnd_down / bnd_up (exact tile mode, may be null): see PathLaunch16.
@@ -1336,44 +1344,16 @@ hipError_t launch_census_paths(const PathFrames& pf, size_t vol_bytes, const Geo
     pl.bnd[1] = bnd_up;
     pl.bnd_slot = bnd_slot;
     const size_t trash_off = (size_t)g.H * g.width1 * g.D;
-    switch (dpl16_for(g.D)) {
-    case 2: launch_paths_dpl<2>(pf, vol_bytes, trash_off, g, pl, items, n_items, st); break;
-    case 4: launch_paths_dpl<4>(pf, vol_bytes, trash_off, g, pl, items, n_items, st); break;
-    case 8: launch_paths_dpl<8>(pf, vol_bytes, trash_off, g, pl, items, n_items, st); break;
-    case 16: launch_paths_dpl<16>(pf, vol_bytes, trash_off, g, pl, items, n_items, st); break;
-    default: launch_paths_dpl<32>(pf, vol_bytes, trash_off, g, pl, items, n_items, st); break;
-    }
+    uint64_t* tr = trace_buffer(n_items);
+    dim3 grid(n_items), block(kWG);
+    with_launch_consts(g.D, 8, [&](auto dpl, auto exact, auto) {     // the path kernel has no NP
+        constexpr int DPL = decltype(dpl)::value;
+        constexpr bool EXACT = decltype(exact)::value;
+        hipLaunchKernelGGL((k_census_paths16<DPL, EXACT>), grid, block, 0, st, pf, vol_bytes, trash_off, g, pl, items,
+                           tr);
+    });
+    trace_dump(tr, n_items, st);
     return hipGetLastError();
-}
-
-template <int DPL, int NP>
-static void launch_wta_dpl(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st)
-{
-    dim3 grid(g.H * wf.n), block(kWG);
-    const size_t lds = wta_lds_bytes<DPL>(g.W);
-    if (wf.outf[0]) {                  // one frame, float rows into a mapped host buffer
-        if (g.D == 16 * DPL)
-            hipLaunchKernelGGL((k_census_wta16f<DPL, true, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
-        else
-            hipLaunchKernelGGL((k_census_wta16f<DPL, false, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
-        return;
-    }
-    if (g.D == 16 * DPL)
-        hipLaunchKernelGGL((k_census_wta16<DPL, true, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
-    else
-        hipLaunchKernelGGL((k_census_wta16<DPL, false, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
-}
-
-template <int NP>
-static void launch_wta_np(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st)
-{
-    switch (dpl16_for(g.D)) {
-    case 2: launch_wta_dpl<2, NP>(wf, vol_bytes, g, out_stride, st); break;
-    case 4: launch_wta_dpl<4, NP>(wf, vol_bytes, g, out_stride, st); break;
-    case 8: launch_wta_dpl<8, NP>(wf, vol_bytes, g, out_stride, st); break;
-    case 16: launch_wta_dpl<16, NP>(wf, vol_bytes, g, out_stride, st); break;
-    default: launch_wta_dpl<32, NP>(wf, vol_bytes, g, out_stride, st); break;
-    }
 }
 
 // WTA + LR of the frames in wf (volumes -> disparity). np: paths summed (8, or 4: the compact
@@ -1381,34 +1361,17 @@ static void launch_wta_np(const WtaFrames& wf, size_t vol_bytes, const Geom& g, 
 hipError_t launch_census_wta(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st,
                              int np)
 {
-    if (np == 4) launch_wta_np<4>(wf, vol_bytes, g, out_stride, st);
-    else launch_wta_np<8>(wf, vol_bytes, g, out_stride, st);
+    with_launch_consts(g.D, np, [&](auto dpl, auto exact, auto npc) {
+        constexpr int DPL = decltype(dpl)::value, NP = decltype(npc)::value;
+        constexpr bool EXACT = decltype(exact)::value;
+        dim3 grid(g.H * wf.n), block(kWG);
+        const size_t lds = wta_lds_bytes<DPL>(g.W);
+        if (wf.outf[0])                    // one frame, float rows into a mapped host buffer
+            hipLaunchKernelGGL((k_census_wta16f<DPL, EXACT, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
+        else
+            hipLaunchKernelGGL((k_census_wta16<DPL, EXACT, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);
+    });
     return hipGetLastError();
-}
-
-template <int DPL, int NP>
-static void launch_fused_dpl(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
-                             size_t trash_off, const Geom& g, const PathLaunch16& pl, const uint32_t* items,
-                             int n_items, size_t out_stride, bool up_wta, hipStream_t st)
-{
-    const int n_census = ((g.W + 63) / 64) * ((g.H + kCensusRows - 1) / kCensusRows) * 2 * cf.n;
-    dim3 grid(n_items + (up_wta ? 0 : g.H * wf.n) + n_census), block(kWG);
-    const size_t lds = std::max({up_wta ? upwta_lds_bytes<DPL>() : wta_lds_bytes<DPL>(g.W),
-                                 sizeof(uint64_t) * rows_lds_codes<DPL>(), (size_t)(kCensusRows + 6) * 72});
-    uint64_t* tr = trace_buffer((int)grid.x);
-    // WTA rows interleaved one per 2.5 blocks (C3 sweeps, first build: after the paths 554
-    // pairs/s, 1/2 498, 1/2.5 578, 1/2.75 580, 1/3 577, 1/3.5 574; with nontemporal volumes,
-    // two interleaved rounds: 1/2.25 655-658, 1/2.5 660-663, 1/2.75 641-657, 1/3.25 649-652,
-    // 1/4 621-635): the memory-bound rows co-run with the VALU-bound sweeps on ~1 slot in 3
-    // instead of waiting for the sweeps' tail
-    static const int period = getenv("SGM_WTA_PERIOD") ? (int)(16 * atof(getenv("SGM_WTA_PERIOD"))) : 40;
-    if (g.D == 16 * DPL)
-        hipLaunchKernelGGL((k_census_fused16<DPL, true, NP>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
-                           pl, items, n_items, out_stride, period, up_wta ? 0 : 1, tr);
-    else
-        hipLaunchKernelGGL((k_census_fused16<DPL, false, NP>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
-                           pl, items, n_items, out_stride, period, up_wta ? 0 : 1, tr);
-    trace_dump(tr, (int)grid.x, st);
 }
 
 hipError_t launch_census_tiles(const CensusFrames& cf, int W, int H, hipStream_t st)
@@ -1416,22 +1379,6 @@ hipError_t launch_census_tiles(const CensusFrames& cf, int W, int H, hipStream_t
     const int n = ((W + 63) / 64) * ((H + kCensusRows - 1) / kCensusRows) * 2 * cf.n;
     if (n > 0) hipLaunchKernelGGL(k_census_tiles, dim3(n), dim3(kWG), 0, st, cf, W, H);
     return hipGetLastError();
-}
-
-template <int NP>
-static void launch_fused_np(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
-                            const Geom& g, const uint32_t* items, int n_items, size_t out_stride, bool up_wta,
-                            hipStream_t st)
-{
-    const PathLaunch16 pl = make_path_launch16(g);
-    const size_t trash_off = (size_t)g.H * g.width1 * g.D;
-    switch (dpl16_for(g.D)) {
-    case 2: launch_fused_dpl<2, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 4: launch_fused_dpl<4, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 8: launch_fused_dpl<8, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    case 16: launch_fused_dpl<16, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    default: launch_fused_dpl<32, NP>(pf, wf, cf, vol_bytes, trash_off, g, pl, items, n_items, out_stride, up_wta, st); break;
-    }
 }
 
 // One launch: path sweeps of the frames in pf (items), WTA of the frames in wf (the previous
@@ -1445,8 +1392,26 @@ hipError_t launch_census_fused(const PathFrames& pf, const WtaFrames& wf, const 
                                const Geom& g, const uint32_t* items, int n_items, size_t out_stride, bool up_wta,
                                hipStream_t st)
 {
-    if (pf.np == 4) launch_fused_np<4>(pf, wf, cf, vol_bytes, g, items, n_items, out_stride, up_wta, st);
-    else launch_fused_np<8>(pf, wf, cf, vol_bytes, g, items, n_items, out_stride, up_wta, st);
+    const PathLaunch16 pl = make_path_launch16(g);
+    const size_t trash_off = (size_t)g.H * g.width1 * g.D;
+    const int n_census = ((g.W + 63) / 64) * ((g.H + kCensusRows - 1) / kCensusRows) * 2 * cf.n;
+    dim3 grid(n_items + (up_wta ? 0 : g.H * wf.n) + n_census), block(kWG);
+    uint64_t* tr = trace_buffer((int)grid.x);
+    // WTA rows interleaved one per 2.5 blocks (C3 sweeps, first build: after the paths 554
+    // pairs/s, 1/2 498, 1/2.5 578, 1/2.75 580, 1/3 577, 1/3.5 574; with nontemporal volumes,
+    // two interleaved rounds: 1/2.25 655-658, 1/2.5 660-663, 1/2.75 641-657, 1/3.25 649-652,
+    // 1/4 621-635): the memory-bound rows co-run with the VALU-bound sweeps on ~1 slot in 3
+    // instead of waiting for the sweeps' tail
+    static const int period = getenv("SGM_WTA_PERIOD") ? (int)(16 * atof(getenv("SGM_WTA_PERIOD"))) : 40;
+    with_launch_consts(g.D, pf.np, [&](auto dpl, auto exact, auto npc) {
+        constexpr int DPL = decltype(dpl)::value, NP = decltype(npc)::value;
+        constexpr bool EXACT = decltype(exact)::value;
+        const size_t lds = std::max({up_wta ? upwta_lds_bytes<DPL>() : wta_lds_bytes<DPL>(g.W),
+                                     sizeof(uint64_t) * rows_lds_codes<DPL>(), (size_t)(kCensusRows + 6) * 72});
+        hipLaunchKernelGGL((k_census_fused16<DPL, EXACT, NP>), grid, block, lds, st, pf, wf, cf, vol_bytes, trash_off, g,
+                           pl, items, n_items, out_stride, period, up_wta ? 0 : 1, tr);
+    });
+    trace_dump(tr, (int)grid.x, st);
     return hipGetLastError();
 }
 

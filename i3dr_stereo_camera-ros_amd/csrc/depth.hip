@@ -12,6 +12,7 @@
 // float division is the correctly rounded one, so results are bit-identical to a float32
 // evaluation of the same C++ expressions.
 #include "sgm_device.h"
+#include "sgm_launch.h"
 
 #pragma clang fp contract(off)
 

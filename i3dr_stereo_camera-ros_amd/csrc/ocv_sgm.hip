@@ -19,6 +19,7 @@
 // 2448x2048 D=480 block-21 config) int32 path volumes, gated per frame by the cost kernel's
 // overflow flag ("OpenCV semantics targets").
 #include "sgm_device.h"
+#include "sgm_launch.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>

@@ -7,6 +7,7 @@
 // of <= maxSize pixels becomes newVal. Component membership is order-independent, so a
 // parallel union-find reproduces OpenCV's sequential flood fill exactly.
 #include "sgm_device.h"
+#include "sgm_launch.h"
 
 namespace sgm {
 

@@ -26,6 +26,7 @@
 // are bit-identical to the scalar C++ evaluation (oracle/sgm_oracle.py rectify_map /
 // cubic_table / remap_cubic).
 #include "sgm_device.h"
+#include "sgm_launch.h"
 
 #include <cmath>
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build an A/B variant of libsgm_hip.so with extra -D flags on some sources (default
-# census_sgm.hip; several: "census_sgm.hip sgm_api.cpp"), the other objects reused from the
+# census_sgm.hip; several: "census_sgm.hip sgm_plan.cpp"), the other objects reused from the
 # in-tree build; load it with SGM_HIP_LIB=i3dr_stereo_camera-ros_amd/lib/variants/NAME/libsgm_hip.so.
 #   bash tools/build_variant.sh NAME "-DSGM_X=1 -DSGM_Y=2" ["source.hip other.cpp"]
 set -eu
