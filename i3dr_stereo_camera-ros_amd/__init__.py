@@ -10,6 +10,8 @@ reference's host-side interface for the hot path so tests read like the referenc
   * `stereo_match`       — generate_disparity.cpp:334-368
   * `process_disparity`  — generate_disparity.cpp:398-456 (x1/16, depth window, MISSING_Z)
   * `parameter_callback` — generate_disparity.cpp:735-845 (cfg sanitising, matcher swap)
+  * `image_cb`           — generate_disparity.cpp:635-713 (raw frames + CameraInfo -> rectified
+                           images + DisparityImage, one device call in every mode)
 
 There is no CPU fallback: if the HIP library is missing or no device is visible, matching
 fails loudly (MatcherHIPSGM.forwardMatch returns -1 exactly like the OpenCV wrapper on an
@@ -389,8 +391,9 @@ class Engine:
                                                     ctypes.c_void_p(stream) if stream else None))
 
     def set_rectification(self, maps_left=None, maps_right=None, map_stride=0, src_width=0, src_height=0):
-        """Raw inputs from now on: device matches rectify inside the census through the
-        (map_x, map_y) device pointers of each camera (None, None: off)."""
+        """Raw inputs from now on: device matches rectify through the (map_x, map_y) device
+        pointers of each camera (None, None: off), inside the census tiles in the census mode and
+        in a pre-pass of each frame in the OCV and BM modes."""
         vp = ctypes.c_void_p
         ml = maps_left or (None, None)
         mr = maps_right or (None, None)
@@ -999,3 +1002,93 @@ def process_disparity(matcher, left_rect, right_rect, f, T, depth_min=0.0, depth
     return dict(image=dmat, f=f, T=T, min_disparity=float(min_disp), max_disparity=float(max_disp),
                 delta_d=1.0 / 16, height=dmat.shape[0], width=dmat.shape[1], encoding="32FC1",
                 step=dmat.shape[1] * 4)
+
+
+def _camera_info(info):
+    """(K, D, R, P) float64 arrays of a CameraInfo given as a mapping, an object with those
+    attributes or a 4-tuple (R None: identity)."""
+    if isinstance(info, dict):
+        info = tuple(info.get(k) for k in "KDRP")
+    elif not isinstance(info, (tuple, list)):
+        info = tuple(getattr(info, k) for k in "KDRP")
+    K, D, R, P = info
+    return (np.asarray(K, np.float64).reshape(3, 3), np.asarray([] if D is None else D, np.float64).ravel(),
+            None if R is None else np.asarray(R, np.float64).reshape(3, 3), np.asarray(P, np.float64).reshape(3, 4))
+
+
+def image_cb(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_min=0.0, depth_max=10.0, state=None):
+    """imageCb() — generate_disparity.cpp:635-713 with everything on the device: rectify() of both
+    raw images, COLOR_BGR2GRAY of colour ones, the match and processDisparity() in one
+    match_device_batch_rect call on the raw frames (mono H x W or colour H x W x 3) plus one
+    disparity_to_msg.
+
+    info_left / info_right: the cameras' K, D, R, P (mapping, object or 4-tuple). The node
+    rectifies at the input size, so the maps have the raw frames' size; they are computed once per
+    calibration and kept in `state` (a dict the caller owns; recomputed when K, D, R, P or the size
+    change). The raw format and grey set follow MatcherHIPSGM._run. With the matcher's interpolation
+    on, the right matcher's parameters run on (right, left) as in forwardMatch (Q3), so the map
+    pairs swap sides too.
+
+    Returns (left_rect, right_rect, msg): the two rectified images the node publishes and the
+    DisparityImage fields of process_disparity(); None when the match failed (this mirror produces
+    the rectified images in the same call as the match, so then it has nothing to publish).
+    Rectification is switched off on the matcher's engine again before returning."""
+    import torch
+    if state is None:
+        state = {}
+    left_raw = np.ascontiguousarray(left_raw, np.uint8)
+    right_raw = np.ascontiguousarray(right_raw, np.uint8)
+    if left_raw.shape != right_raw.shape or left_raw.ndim not in (2, 3) or (left_raw.ndim == 3 and left_raw.shape[2] != 3):
+        sys.stderr.write("Images MUST be the same resolution\n")
+        return None
+    h, w = left_raw.shape[:2]
+    ch = 3 if left_raw.ndim == 3 else 1
+    eng = matcher._engine_for()
+    cams = [_camera_info(info_left), _camera_info(info_right)]
+    key = (h, w) + tuple(None if a is None else a.tobytes() for c in cams for a in c)
+    try:
+        if state.get("key") != key:
+            maps = torch.empty((4, h, w), dtype=torch.float32, device="cuda")
+            stream = _side_stream(torch)
+            for i, (K, D, R, P) in enumerate(cams):
+                eng.rectify_map(K, D, R, P, w, h, maps[2 * i].data_ptr(), maps[2 * i + 1].data_ptr(), w,
+                                stream.cuda_stream)
+            stream.synchronize()
+            state["key"], state["maps"] = key, maps
+            state["map_builds"] = state.get("map_builds", 0) + 1
+        maps = state["maps"]
+        params, bm = matcher.params, matcher.bm_params
+        dl, dr = torch.as_tensor(left_raw).cuda(), torch.as_tensor(right_raw).cuda()
+        ml, mr = (maps[0].data_ptr(), maps[1].data_ptr()), (maps[2].data_ptr(), maps[3].data_ptr())
+        rect = torch.empty((2,) + left_raw.shape, dtype=torch.uint8, device="cuda")
+        first, second, rl, rr = dl, dr, rect[0], rect[1]
+        if matcher.interpolate:
+            params, bm = right_matcher_params(params), right_matcher_bm_params(bm)
+            first, second, rl, rr, ml, mr = dr, dl, rect[1], rect[0], mr, ml
+        eng.set_params(params)
+        eng.set_census_paths(matcher.census_paths)
+        eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
+        if params.mode == MODE_OCV_BM:
+            eng.set_bm_params(bm)
+        disp = torch.empty((h, w), dtype=torch.int16, device="cuda")
+        msg = torch.empty((h, w), dtype=torch.float32, device="cuda")
+        min_disp = np.float32(T * f / depth_max)
+        with np.errstate(divide="ignore"):
+            max_disp = np.float32(T * f / depth_min) if depth_min != 0 else np.float32(np.inf)  # Q8
+        stream = _side_stream(torch)
+        eng.set_rectification(ml, mr, w, w, h)
+        try:
+            eng.match_device_batch_rect([first.data_ptr()], [second.data_ptr()], w, h, w * ch, [rl.data_ptr()],
+                                        [rr.data_ptr()], w * ch, [disp.data_ptr()], w, stream.cuda_stream)
+            eng.disparity_to_msg(disp.data_ptr(), w, w, h, min_disp, max_disp, msg.data_ptr(), w, stream.cuda_stream)
+            stream.synchronize()
+        finally:
+            eng.set_rectification()
+    except SGMError as e:      # the matcher wrappers' catch -> -1, then "Failed to compute stereo match"
+        what = "HIP StereoBM" if matcher.mode == MODE_OCV_BM else "HIP SGM"
+        sys.stderr.write("Error in %s parameters\n%s\nFailed to compute stereo match\n" % (what, e))
+        return None
+    dmat = msg.cpu().numpy()
+    out = dict(image=dmat, f=f, T=T, min_disparity=float(min_disp), max_disparity=float(max_disp),
+               delta_d=1.0 / 16, height=h, width=w, encoding="32FC1", step=w * 4)
+    return rect[0].cpu().numpy(), rect[1].cpu().numpy(), out

@@ -21,6 +21,9 @@
 //  k_bgr2gray      cv::cvtColor(COLOR_BGR2GRAY) 8UC3 -> 8UC1 (generate_disparity.cpp:406-416) in
 //                  its 14-bit (OpenCV 3.x) or 15-bit (4.x) coefficients, over the bytes in memory
 //                  order; restated, unverified against OpenCV.
+//  k_rectify_pair  the pre-pass of the OCV / BM modes on raw frames: both images of a pair
+//                  remapped (and, for colour, converted after the remap) into the handle's grey
+//                  planes and the caller's rectified images, 4 pixels per thread.
 //
 // FMA contraction is off for this file: the double map and the float cubic coefficients
 // are bit-identical to the scalar C++ evaluation (oracle/sgm_oracle.py rectify_map /
@@ -125,6 +128,114 @@ __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ sr
     } else {
         const int n = min(4, W - x);
         for (int i = 0; i < n; i++) d[i] = (uint8_t)gray_px(s[3 * i], s[3 * i + 1], s[3 * i + 2], set);
+    }
+}
+
+// The node's imageCb ahead of an OCV / BM match (generate_disparity.cpp:651-652, :406-416): both
+// raw images of a frame pair rectified in one launch, blockIdx.z selects the image. CH == 1:
+// grey = remap(raw); CH == 3: the colour pixel is remapped first and then converted (the node's
+// order: a grey image is never remapped). The grey plane (row stride W) feeds the matcher, the
+// rectified image (8UC1 / 8UC3, may be null) goes to the caller.
+// A thread owns 4 consecutive pixels of a row: its two map segments as one 16-byte load each, the
+// grey bytes as one dword and the 12 colour bytes as three, wherever the segment is whole and
+// the address aligned; element by element otherwise (odd strides or bases, the row's tail).
+// The remap itself runs transposed: in step i lane t computes pixel 64 i + t of its wave's 256,
+// so the 16 tap loads of a step read neighbouring bytes across the wave as in k_remap_cubic
+// (with each lane on its own 4 pixels they are 4 pixels apart: 0.100 against 0.082 ms for the
+// mono pair at 2448 x 2048). The map values go to the computing lanes and the pixels back to
+// their owners through LDS (12 KB per block, a region per wave). No pixel needs a neighbourhood,
+// so there is no image tile and no halo: the 4 x 4 taps come from L1 / L2.
+struct RectPair {
+    const uint8_t* src0; const uint8_t* src1;     // raw images, sw x sh, row stride sstride bytes
+    const float* mx0; const float* my0;           // maps of image 0 / 1, W x H, row stride mstride floats
+    const float* mx1; const float* my1;
+    uint8_t* gray0; uint8_t* gray1;               // W x H, row stride W
+    uint8_t* rect0; uint8_t* rect1;               // W x H x CH, row stride rstride bytes, or null
+    size_t sstride, mstride, rstride;
+    int sw, sh, W, H, set;
+    const int16_t* tab;
+};
+
+template <int CH>
+__global__ __launch_bounds__(256) void k_rectify_pair(RectPair p)
+{
+    __shared__ __align__(16) float s_mx[4][256];          // per wave: the maps of its 256 pixels
+    __shared__ __align__(16) float s_my[4][256];
+    __shared__ __align__(16) uint32_t s_px[4][256];       // ... and their remapped values (CH bytes each)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * 256, x = x0 + lane * 4, y = blockIdx.y * 4 + wv;
+    const bool row = y < p.H, own = row && x < p.W;
+    const bool z = blockIdx.z != 0;
+    const uint8_t* __restrict__ src = z ? p.src1 : p.src0;
+    const int n = min(4, p.W - x);
+    if (own) {
+        const float* rx = (z ? p.mx1 : p.mx0) + (size_t)y * p.mstride + x;
+        const float* ry = (z ? p.my1 : p.my0) + (size_t)y * p.mstride + x;
+        float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+        if (n == 4 && (((uintptr_t)rx | (uintptr_t)ry) & 15) == 0) {
+            a = *(const float4*)rx; b = *(const float4*)ry;
+        } else {
+            a.x = rx[0]; b.x = ry[0];
+            if (n > 1) { a.y = rx[1]; b.y = ry[1]; }
+            if (n > 2) { a.z = rx[2]; b.z = ry[2]; }
+            if (n > 3) { a.w = rx[3]; b.w = ry[3]; }
+        }
+        *(float4*)&s_mx[wv][4 * lane] = a;
+        *(float4*)&s_my[wv][4 * lane] = b;
+    }
+    __syncthreads();
+    // pixels past the row's end are not computed (their map values were not read either)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int k = 64 * i + lane;
+        if (row && x0 + k < p.W) {
+            const float fx = s_mx[wv][k], fy = s_my[wv][k];
+            s_px[wv][k] = CH == 3 ? remap_cubic_px3(src, p.sstride, p.sw, p.sh, fx, fy, p.tab)
+                                  : (uint32_t)remap_cubic_px(src, p.sstride, p.sw, p.sh, fx, fy, p.tab);
+        }
+    }
+    __syncthreads();
+    if (!own) return;
+    const uint4 q = *(const uint4*)&s_px[wv][4 * lane];
+    const uint32_t v0 = q.x, v1 = n > 1 ? q.y : 0, v2 = n > 2 ? q.z : 0, v3 = n > 3 ? q.w : 0;
+    uint8_t* g = (z ? p.gray1 : p.gray0) + (size_t)y * p.W + x;
+    uint8_t* r = z ? p.rect1 : p.rect0;
+    if (r) r += (size_t)y * p.rstride + (size_t)CH * x;
+    uint32_t gq = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);      // CH == 1: the four grey bytes
+    if (CH == 3) {
+        if (r) {
+            if (n == 4 && ((uintptr_t)r & 3) == 0) {
+                ((uint32_t*)r)[0] = v0 | (v1 << 24);
+                ((uint32_t*)r)[1] = (v1 >> 8) | (v2 << 16);
+                ((uint32_t*)r)[2] = (v2 >> 16) | (v3 << 8);
+            } else {
+                r[0] = (uint8_t)v0; r[1] = (uint8_t)(v0 >> 8); r[2] = (uint8_t)(v0 >> 16);
+                if (n > 1) { r[3] = (uint8_t)v1; r[4] = (uint8_t)(v1 >> 8); r[5] = (uint8_t)(v1 >> 16); }
+                if (n > 2) { r[6] = (uint8_t)v2; r[7] = (uint8_t)(v2 >> 8); r[8] = (uint8_t)(v2 >> 16); }
+                if (n > 3) { r[9] = (uint8_t)v3; r[10] = (uint8_t)(v3 >> 8); r[11] = (uint8_t)(v3 >> 16); }
+            }
+        }
+        gq = (uint32_t)gray_px(v0 & 255, (v0 >> 8) & 255, v0 >> 16, p.set) |
+             ((uint32_t)gray_px(v1 & 255, (v1 >> 8) & 255, v1 >> 16, p.set) << 8) |
+             ((uint32_t)gray_px(v2 & 255, (v2 >> 8) & 255, v2 >> 16, p.set) << 16) |
+             ((uint32_t)gray_px(v3 & 255, (v3 >> 8) & 255, v3 >> 16, p.set) << 24);
+    } else if (r) {
+        if (n == 4 && ((uintptr_t)r & 3) == 0) {
+            *(uint32_t*)r = gq;
+        } else {
+            r[0] = (uint8_t)gq;
+            if (n > 1) r[1] = (uint8_t)(gq >> 8);
+            if (n > 2) r[2] = (uint8_t)(gq >> 16);
+            if (n > 3) r[3] = (uint8_t)(gq >> 24);
+        }
+    }
+    if (n == 4 && ((uintptr_t)g & 3) == 0) {
+        *(uint32_t*)g = gq;
+    } else {
+        g[0] = (uint8_t)gq;
+        if (n > 1) g[1] = (uint8_t)(gq >> 8);
+        if (n > 2) g[2] = (uint8_t)(gq >> 16);
+        if (n > 3) g[3] = (uint8_t)(gq >> 24);
     }
 }
 
@@ -240,6 +351,20 @@ hipError_t launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, size_t sstr
 {
     hipLaunchKernelGGL(k_bgr2gray, dim3((W + 255) / 256, (H + 3) / 4, src1 ? 2 : 1), dim3(256), 0, st, src0, src1,
                        sstride, W, H, dst0, dst1, dstride, set);
+    return hipGetLastError();
+}
+
+// Both raw images of a frame pair (ch 1: 8UC1, 3: 8UC3, sstride / rstride in bytes) through
+// rect.map into the grey planes (row stride W) and, where not null, the rectified images.
+hipError_t launch_rectify_pair(const RectifyIn& rect, const uint8_t* rawL, const uint8_t* rawR, size_t sstride, int ch,
+                               int gray_set, int W, int H, uint8_t* grayL, uint8_t* grayR, uint8_t* rectL,
+                               uint8_t* rectR, size_t rstride, hipStream_t st)
+{
+    const RectPair p{rawL, rawR, rect.map[0], rect.map[1], rect.map[2], rect.map[3], grayL, grayR, rectL, rectR,
+                     sstride, rect.map_stride, rstride, rect.src_w, rect.src_h, W, H, gray_set, rect.tab};
+    const dim3 grid((W + 255) / 256, (H + 3) / 4, 2);
+    if (ch == 3) hipLaunchKernelGGL(k_rectify_pair<3>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_rectify_pair<1>, grid, dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

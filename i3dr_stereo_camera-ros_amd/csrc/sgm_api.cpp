@@ -221,7 +221,7 @@ int sgm_match_device(sgm_handle* h, const uint8_t* dL, const uint8_t* dR, int W,
                      size_t out_stride, void* stream)
 {
     if (!h) return SGM_ERR_ARG;
-    if (h->rect_on) {          // raw inputs: the census-fused rectification path
+    if (h->rect_on) {          // raw inputs: rectified in the census tiles or by the OCV / BM pre-pass
         const uint8_t* l1[1] = {dL};
         const uint8_t* r1[1] = {dR};
         int16_t* o1[1] = {dOut};
@@ -258,16 +258,17 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
     for (int i = 0; i < n; i++)
         if (!dLs[i] || !dRs[i] || !outs[i]) return fail(h, SGM_ERR_ARG, "null frame pointer");
     if (n == 0) return SGM_OK;
-    if (h->rect_on && h->cfg.params.mode != SGM_MODE_CENSUS8)
-        return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification runs in the census mode (use sgm_remap_cubic)");
     Geom g;
     Layout l;
     int rc = make_geom(h->cfg.params, W, H, g, h->err, &h->cfg.bm);
     if (rc) return rc;
     if (h->rect_on && g.width1 <= 0)
         return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
+    // raw frames: the census mode rectifies inside its tiles, the OCV / BM modes in a pre-pass
+    // of each frame (k_rectify_pair) into the handle's grey planes
+    const bool prepass = h->rect_on && h->cfg.params.mode != SGM_MODE_CENSUS8;
     const bool pipelined = h->cfg.params.mode == SGM_MODE_CENSUS8 && (n >= 2 || h->rect_on) && g.width1 > 0;
-    rc = prepare(h, h->cfg, W, H, false, g, l, pipelined ? batch_group(n) : 0);
+    rc = prepare(h, h->cfg, W, H, false, g, l, pipelined ? batch_group(n) : 0, prepass);
     if (rc) return rc;
     hipStream_t own = h->stream;
     if (stream) h->stream = (hipStream_t)stream;
@@ -276,9 +277,13 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
     } else if (pipelined) {
         rc = run_batch_census(h, l, g, dLs, dRs, n, stride, outs, out_stride, rectLs, rectRs, rect_stride);
     } else if (h->cfg.params.mode != SGM_MODE_CENSUS8 && ocv_batch_lanes(n) > 1 && !h->profiling) {
-        rc = run_batch_ocv(h, l, g, W, H, dLs, dRs, n, stride, outs, out_stride);
+        rc = run_batch_ocv(h, l, g, W, H, dLs, dRs, n, stride, outs, out_stride, rectLs, rectRs, rect_stride);
     } else {
-        for (int i = 0; i < n && rc == 0; i++) rc = run_pipeline(h, l, g, dLs[i], dRs[i], stride, outs[i], out_stride);
+        for (int i = 0; i < n && rc == 0; i++) {
+            const RectOut ro{rectLs ? rectLs[i] : nullptr, rectRs ? rectRs[i] : nullptr, rect_stride};
+            rc = run_pipeline(h, l, g, dLs[i], dRs[i], stride, outs[i], out_stride, nullptr, nullptr, 0,
+                              prepass ? &ro : nullptr);
+        }
     }
     if (!rc) rc = mark_done(h, h->stream);
     h->stream = own;

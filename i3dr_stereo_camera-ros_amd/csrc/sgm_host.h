@@ -73,7 +73,8 @@ struct sgm_handle {
     int items_cap = 0;
     std::string items_key[2];      // geometry + workspace each device copy (single / group) belongs to
     int16_t* cubic_tab = nullptr;  // device INTER_CUBIC weight table (sgm_remap_cubic), built once
-    bool rect_on = false;          // sgm_set_rectification: batch inputs are raw, rectified in the census
+    bool rect_on = false;          // sgm_set_rectification: device-match inputs are raw (rectified in the census
+                                   // tiles, or by the k_rectify_pair pre-pass of the OCV / BM modes)
     sgm::RectifyIn rect{};
     // exact tile mode (sgm_match_tiled_exact): one handle per row band, each with a second
     // stream for its upward sweeps and four events (census, down, up, gather)
@@ -137,7 +138,7 @@ struct Layout {
     size_t planes = 0, bufA = 0, bufB = 0, ovols = 0, ovf = 0;  // ocv
     size_t ores = 0;                                       // ocv: per-pixel results of k_ocv_vwta
     size_t bmL = 0, bmR = 0, bmV = 0;                      // bm: pre-filtered images, HBM column sums
-    size_t grayL = 0, grayR = 0;                           // ocv / bm with colour frames: the grey planes
+    size_t grayL = 0, grayR = 0;                           // ocv / bm with colour or raw frames: the grey planes
     sgm::BmPlan bm{};                                      // bm: tiling of the fused kernel
     size_t tmp = 0, lab = 0, cnt = 0;                      // post
     size_t inL = 0, inR = 0, out = 0, outf = 0;            // host-API staging (int16 / float out)
@@ -186,12 +187,20 @@ struct FrameHooks {
     virtual ~FrameHooks() = default;
 };
 
+// OCV / BM modes on raw frames (sgm_set_rectification): where one frame's rectified images go
+// (null: not wanted; stride in bytes). Passing one to run_pipeline makes its inputs raw frames.
+struct RectOut {
+    uint8_t* L = nullptr;
+    uint8_t* R = nullptr;
+    size_t stride = 0;
+};
+
 // sgm_plan.cpp
 int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err, const sgm_bm_params* bm = nullptr);
 bool use_median(const sgm_params& p);
 bool use_speckle(const sgm_params& p);
 int speckle_scale(int mode);
-Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group = 0, int n_cu = 0);
+Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group = 0, int n_cu = 0, bool rect = false);
 Layout make_post_layout(const sgm_params& p, const Geom& g);
 int batch_group(int n);
 bool ocv_vwta_on(const Geom& g, int fullDP);
@@ -210,17 +219,19 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
              size_t tmp_off = 0);
 int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* dL, const uint8_t* dR, size_t stride,
                  int16_t* dOut, size_t out_stride, const std::function<hipEvent_t()>& copy_r = nullptr,
-                 float* outf = nullptr, size_t outf_stride = 0);
+                 float* outf = nullptr, size_t outf_stride = 0, const RectOut* raw = nullptr);
 int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* const* dLs,
                      const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
                      uint8_t* const* rectLs = nullptr, uint8_t* const* rectRs = nullptr, size_t rect_stride = 0,
                      FrameHooks* hooks = nullptr);
 int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H, const uint8_t* const* dLs,
-                  const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride);
+                  const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
+                  uint8_t* const* rectLs = nullptr, uint8_t* const* rectRs = nullptr, size_t rect_stride = 0);
 int raw_format_status(sgm_handle* h, const MatchConfig& c);
 int refuse_colour(sgm_handle* h, const char* what);
 size_t raw_bpp(const sgm_handle* h);
-int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group = 0);
+int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group = 0,
+            bool rect = false);
 int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, size_t stride, void* out,
                size_t out_stride, bool f32);
 

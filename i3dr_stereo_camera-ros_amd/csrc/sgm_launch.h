@@ -35,6 +35,9 @@ hipError_t launch_remap_cubic_c3(const uint8_t* src, size_t sstride, int sw, int
                                  hipStream_t st);
 hipError_t launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, size_t sstride, int W, int H, uint8_t* dst0,
                            uint8_t* dst1, size_t dstride, int set, hipStream_t st);
+hipError_t launch_rectify_pair(const RectifyIn& rect, const uint8_t* rawL, const uint8_t* rawR, size_t sstride, int ch,
+                               int gray_set, int W, int H, uint8_t* grayL, uint8_t* grayR, uint8_t* rectL,
+                               uint8_t* rectR, size_t rstride, hipStream_t st);
 void cubic_table(int16_t* tab);
 bool rectify_inverse(const double* P, const double* R, double* ir);
 

@@ -164,10 +164,12 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
 // image's census waits on that event (a pageable copy can hold the host until it is done, so the
 // left census must already be queued). outf (census mode without median / speckles): the WTA
 // writes the final rows as float to outf (a mapped host buffer, row stride outf_stride floats)
-// and dOut is not written.
+// and dOut is not written. raw (OCV / BM modes, rectification set): dL / dR are raw frames
+// (stride = raw stride) that the k_rectify_pair pre-pass rectifies into the grey planes; *raw
+// names the frame's rectified-output images.
 int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* dL, const uint8_t* dR, size_t stride,
                  int16_t* dOut, size_t out_stride, const std::function<hipEvent_t()>& copy_r, float* outf,
-                 size_t outf_stride)
+                 size_t outf_stride, const RectOut* raw)
 {
     const sgm_params& p = h->cfg.params;
     char* ws = (char*)h->ws.base;
@@ -182,7 +184,18 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
     StageRec rec{h};
     if (h->profiling) h->prof_frames++;
     const int ch = h->cfg.raw_ch == 3 ? 3 : 1;
-    if (ch == 3 && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
+    if (raw && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
+        // raw frames (the node's imageCb): both images through the handle's maps into the grey
+        // planes, colour converted after the remap, then the unchanged pipeline on those. Bytes:
+        // 16 B/px of maps and ch B/px of source per pair read, 2 B/px of grey and ch B/px per
+        // rectified image written.
+        uint8_t* GL = (uint8_t*)(ws + l.grayL);
+        uint8_t* GR = (uint8_t*)(ws + l.grayR);
+        rec.begin("rectify", (16 + 2 * ch + 2 + ch * ((raw->L ? 1 : 0) + (raw->R ? 1 : 0))) * WH);
+        HIP_TRY(sgm::launch_rectify_pair(h->rect, dL, dR, stride, ch, h->cfg.gray_set, g.W, g.H, GL, GR, raw->L,
+                                         raw->R, raw->stride, st), "rectify");
+        dL = GL; dR = GR; stride = g.W;
+    } else if (ch == 3 && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
         // colour frames: COLOR_BGR2GRAY of both images into the handle's grey planes, then the
         // unchanged pipeline on those (the census mode converts inside its tiles instead)
         uint8_t* GL = (uint8_t*)(ws + l.grayL);
@@ -464,7 +477,7 @@ size_t raw_bpp(const sgm_handle* h) { return h->cfg.raw_ch == 3 ? 3 : 1; }
 
 // Geometry, layout and workspace of a W x H frame under configuration c (the handle's own, or
 // a copy of it that a debug entry point adjusted).
-int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group)
+int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group, bool rect)
 {
     int rc = make_geom(c.params, W, H, g, h->err, &c.bm);
     if (rc) return rc;
@@ -473,7 +486,7 @@ int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geo
                                           std::to_string(c.census_paths));
     if ((rc = raw_format_status(h, c))) return rc;
     if ((rc = ensure_stream(h))) return rc;
-    l = make_layout(c, g, host_io, group, h->n_cu);
+    l = make_layout(c, g, host_io, group, h->n_cu, rect);
     // the uploaded path work list lives in the workspace: any other use of it invalidates it
     if (c.params.mode != SGM_MODE_CENSUS8) { h->items_key[0].clear(); h->items_key[1].clear(); }
     return ensure_ws(h, l.total);
@@ -486,9 +499,13 @@ int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geo
 // holds their workspace (the shipped 2448x2048 D=480 block-21 frame needs 27-70 GB per
 // workspace, by mode and OpenCV build), and a lane whose allocation fails ends the list. Every
 // lane starts after the work already on h->stream, and h->stream waits for every lane, so the
-// call keeps the single-stream contract.
+// call keeps the single-stream contract. With h->rect_on the frames are raw: every lane gets the
+// handle's rectification state (the maps and the weight table stay the handle's) and plans its
+// workspace with the grey planes, and frame i's rectified-output pointers go to the lane that
+// runs frame i.
 int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H, const uint8_t* const* dLs,
-                  const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride)
+                  const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
+                  uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride)
 {
     const int Smax = ocv_batch_lanes(n);
     size_t free_b = 0, total_b = 0;
@@ -505,9 +522,11 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
         if (extra + reserve > free_b) break;
         if (!q && sgm_create(&q, h->device) != SGM_OK) break;
         q->cfg = h->cfg;
+        q->rect = h->rect;
+        q->rect_on = h->rect_on;
         Geom gq;
         Layout lq;
-        if (prepare(q, q->cfg, W, H, false, gq, lq) != SGM_OK) {   // e.g. an allocation failure: fewer lanes
+        if (prepare(q, q->cfg, W, H, false, gq, lq, 0, h->rect_on) != SGM_OK) {   // e.g. an allocation failure: fewer lanes
             q->err.clear();
             break;
         }
@@ -524,7 +543,9 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
     for (int i = 0; i < n; i++) {
         const int s = i % S;
         sgm_handle* q = s ? h->par[s - 1] : h;
-        const int rc = run_pipeline(q, l[s], g[s], dLs[i], dRs[i], stride, outs[i], out_stride);
+        const RectOut ro{rectLs ? rectLs[i] : nullptr, rectRs ? rectRs[i] : nullptr, rect_stride};
+        const int rc = run_pipeline(q, l[s], g[s], dLs[i], dRs[i], stride, outs[i], out_stride, nullptr, nullptr, 0,
+                                    h->rect_on ? &ro : nullptr);
         if (rc) return q == h ? rc : fail(h, rc, q->err);
     }
     for (int s = 1; s < S; s++) {

@@ -143,7 +143,9 @@ static bool use_up_wta()
     return !e || std::atoi(e) != 0;
 }
 
-Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group, int n_cu)
+// rect: the frames are raw (sgm_set_rectification) and the mode is OCV or BM, whose pre-pass
+// rectifies them into the grey planes.
+Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group, int n_cu, bool rect)
 {
     const sgm_params& p = c.params;
     const int ch = c.raw_ch;
@@ -201,7 +203,7 @@ Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group,
     }
     l.tmp = take(WH * 2 * (size_t)std::max(group, 1));   // raw disparity before the median (per frame of a group)
     if (p.speckle_window_size > 0) { l.lab = take(WH * 4); l.cnt = take(WH * 4); }
-    if (ch == 3 && p.mode != SGM_MODE_CENSUS8) { l.grayL = take(WH); l.grayR = take(WH); }
+    if ((ch == 3 || rect) && p.mode != SGM_MODE_CENSUS8) { l.grayL = take(WH); l.grayR = take(WH); }
     if (host_io) { l.inL = take(WH * ch); l.inR = take(WH * ch); l.out = take(WH * 2); l.outf = take(WH * 4); }
     l.total = off;
     return l;

@@ -198,9 +198,10 @@ int  sgm_get_census_paths(const sgm_handle* h, int* paths);
  *    the node publishes and what sgm_depth_points(channels = 3) colours the cloud with.
  *  - the order is the node's: the colour image is remapped first, then converted; a grey image
  *    is never remapped. The census mode does both inside its census tiles (no grey image
- *    exists in memory); the OCV and BM modes convert both images into per-handle grey planes
- *    first (profiling stage `gray`) and run their pipelines unchanged (they still refuse fused
- *    rectification: rectify with sgm_remap_cubic_c3, the match converts).
+ *    exists in memory); the OCV and BM modes produce both grey images in per-handle planes
+ *    first and run their pipelines unchanged on those: a conversion alone for rectified frames
+ *    (profiling stage `gray`), or, under sgm_set_rectification, the pre-pass that remaps the
+ *    colour pixel and then converts it (stage `rectify`, which replaces `gray`).
  *  - sgm_match_batch, sgm_match_tiled, sgm_match_tiled_device and sgm_match_tiled_exact return
  *    SGM_ERR_UNSUPPORTED (their sub-handles do not carry the format yet).
  * sgm_stage_bytes of the census stages then counts 3 B/px read per image, plus 3 B/px per
@@ -378,18 +379,29 @@ int  sgm_remap_cubic_c3(sgm_handle* h, const uint8_t* d_src, size_t src_stride, 
  * Asynchronous on `stream`.                                                                 */
 int  sgm_bgr2gray(sgm_handle* h, const uint8_t* d_src, size_t src_stride, int width, int height,
                   uint8_t* d_dst, size_t dst_stride, int gray_set, void* stream);
-/* Rectification fused into the census (census mode): after this call the device matches
- * (sgm_match_device, sgm_match_device_batch, sgm_match_device_batch_rect) take RAW images of
- * src_width x src_height (their stride argument = the raw stride) and rectify them inside
- * the census tiles through the maps (W x H = the match geometry, e.g. from sgm_rectify_map;
- * left x/y, right x/y). The maps must stay valid while set. All four maps NULL switches it
- * off. sgm_match (host buffers) returns SGM_ERR_UNSUPPORTED while it is on, as do the OCV
- * modes (rectify those with sgm_remap_cubic).                                               */
+/* Rectification ahead of the matcher, as the node's imageCb does it (generate_disparity.cpp:
+ * 651-652): after this call the device matches (sgm_match_device, sgm_match_device_batch,
+ * sgm_match_device_batch_rect) take RAW images of src_width x src_height (their stride
+ * argument = the raw stride) and rectify them through the maps (W x H = the match geometry,
+ * e.g. from sgm_rectify_map; left x/y, right x/y), in every mode:
+ *  - SGM_MODE_CENSUS8 remaps inside its census tiles (no rectified image exists in memory
+ *    unless one is requested);
+ *  - SGM_MODE_OCV_SGBM5, SGM_MODE_OCV_HH8 and SGM_MODE_OCV_BM run one pre-pass launch per
+ *    frame pair (profiling stage `rectify`) that remaps both images into per-handle grey
+ *    planes, then their unchanged pipelines on those. sgm_stage_bytes of that stage: 16 B/px
+ *    of maps and 2 * channels B/px of source read, 2 B/px of grey and channels B/px per
+ *    requested rectified image written.
+ * The maps must stay valid while set. All four maps NULL switches it off. A frame without a
+ * disparity window (width <= the disparity span) is SGM_ERR_UNSUPPORTED while it is on, as are
+ * sgm_match / sgm_match_f32 (host buffers) and sgm_match_tiled_device.                       */
 int  sgm_set_rectification(sgm_handle* h, const float* d_map_xl, const float* d_map_yl, const float* d_map_xr,
                            const float* d_map_yr, size_t map_stride, int src_width, int src_height);
 /* sgm_match_device_batch that also returns the rectified images (d_rect_lefts /
  * d_rect_rights: arrays of n device pointers, W x H u8 with row stride rect_stride; either
- * array may be NULL). Needs sgm_set_rectification.                                          */
+ * array may be NULL, and an image that is not requested is not written). Rectified outputs
+ * need sgm_set_rectification; with it, every mode fills them: the raw frames of an OCV or BM
+ * batch are rectified frame by frame on the lane that matches them. With 3 channels
+ * (sgm_set_raw_format) they are 8UC3 and rect_stride is in bytes (>= 3 * width).             */
 int  sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* d_raw_lefts, const uint8_t* const* d_raw_rights,
                                  int n_frames, int width, int height, size_t raw_stride,
                                  uint8_t* const* d_rect_lefts, uint8_t* const* d_rect_rights, size_t rect_stride,
