@@ -46,6 +46,10 @@
 #ifndef SGM_UPWTA_PRIO
 #define SGM_UPWTA_PRIO 0   // s_setprio of the up+WTA blocks (0: default priority)
 #endif
+#ifndef SGM_UPWTA_TTAB
+#define SGM_UPWTA_TTAB 16  // up+WTA blocks of DPL >= this read the uniqueness threshold T(minS) from an LDS table
+                           // (below: computed per step; measured slower with the table at DPL 8, C2)
+#endif
 #ifndef SGM_ROWS_LPL8
 #define SGM_ROWS_LPL8 0    // 1: row sweeps with 8 lanes per path line for D <= 256 (RowsCfg; measured slower)
 #endif
@@ -585,15 +589,52 @@ struct UpWta {
     uint64_t* res;           // [H][W] results + 64 trash slots
 };
 struct WtaPix { int best, minS, d16; bool rej; };   // one pixel's WTA result (wta_pix16)
-template <int DPL, bool EXACT>
+// Dword j of NV u8 volumes summed into u16 pairs: e = the even bytes' sums, o = the odd bytes'.
+// Only the odd bytes are extracted: the plain wrapping sum of the raw dwords is e + (o << 8)
+// (mod 2^32), and every half of e is <= NV * 255 < 2^16, so the subtraction gives e exactly.
+template <int NV, int NWD>
+__device__ __forceinline__ void sum_eo(const uint32_t (&v)[NV][NWD], int j, uint32_t& e, uint32_t& o)
+{
+    static_assert(NV * 255 < 65536, "the even halves must not carry");
+    uint32_t sv = 0, so = 0;
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        sv += v[k][j];
+        so += __builtin_amdgcn_perm(0u, v[k][j], 0x0c030c01u);
+    }
+    e = sv - (so << 8);
+    o = so;
+}
+// wta_pix16 in two halves: everything that needs the 16 lanes of the pixel (wta_tot16), then the
+// per-pixel arithmetic on its outputs (wta_tail)
+struct WtaTot { int best, minS, sm, sp, T, tot; };
+template <int DPL, bool EXACT, typename TF>
+__device__ __forceinline__ WtaTot wta_tot16(const uint32_t (&E)[(DPL + 3) / 4], const uint32_t (&O)[(DPL + 3) / 4],
+                                            int p, TF thresh, uint32_t* srow);
+__device__ __forceinline__ WtaPix wta_tail(const WtaTot& t, const Geom& g);
+template <int DPL, bool EXACT, typename TF>
 __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], const uint32_t (&O)[(DPL + 3) / 4],
-                                            int p, const Geom& g, float inv_u, uint32_t* srow);
+                                            int p, const Geom& g, TF thresh, uint32_t* srow)
+{
+    return wta_tail(wta_tot16<DPL, EXACT>(E, O, p, thresh, srow), g);
+}
+__device__ __forceinline__ int wta_thresh(int minS, int uniq, float inv_u);
 template <int DPL, bool EXACT>
 __device__ __forceinline__ void wta_emask(int p, const Geom& g, uint32_t (&emaskE)[(DPL + 3) / 4],
                                           uint32_t (&emaskO)[(DPL + 3) / 4]);
-// LDS of an up+WTA block: the row sweep's code buffers, then 16 lines x 32 x NWD S dwords
+// LDS of an up+WTA block: the row sweep's code buffers, then 16 line rows, then the uniqueness
+// thresholds T(minS) as u16 (minS <= 8 * 255; kThreshN entries). A line row: 32 x NWD S dwords,
+// then 16 slots of 16 B, the deferred WTA tails' inputs (p16_rows): one address register serves
+// both, and a 17th slot's worth of padding keeps the 4 lines of a wave off each other's banks.
+constexpr int kThreshN = 2048;
+__host__ __device__ constexpr bool upwta_ttab(int dpl) { return dpl >= SGM_UPWTA_TTAB; }
+__host__ __device__ constexpr int upwta_line_dwords(int nwd) { return 32 * nwd + 17 * 4; }
 template <int DPL>
-__host__ __device__ constexpr size_t upwta_lds_bytes() { return (size_t)8 * 2 * RowSeg<DPL, 16>::BUF + (size_t)16 * 32 * ((DPL + 3) / 4) * 4; }
+__host__ __device__ constexpr size_t upwta_lds_bytes()
+{
+    return (size_t)8 * 2 * RowSeg<DPL, 16>::BUF + (size_t)16 * upwta_line_dwords((DPL + 3) / 4) * 4 +
+           (upwta_ttab(DPL) ? (size_t)kThreshN * 2 : 0);
+}
 
 // NL lines of direction dir starting at base column xb (DPL disparities per lane, LPL
 // lanes per line; lds: 2 * RowSeg<DPL, LPL>::BUF codes).
@@ -656,14 +697,20 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     seg_load<DPL, LPL>(R1, sa, g, rx, ry, xb, min(s0 + 1, s1 - 1));
     seg_load<DPL, LPL>(R2, sa, g, rx, ry, xb, min(s0 + 2, s1 - 1));
     seg_load<DPL, LPL>(R3, sa, g, rx, ry, xb, min(s0 + 3, s1 - 1));
+    // up+WTA (FUSE): the uniqueness threshold of every possible minS, once per block (uniq is fixed
+    // for the launch): the step reads one u16 instead of redoing the division in every lane
+    constexpr int NWD = (DPL + 3) / 4;
+    const uint16_t* ttab = (const uint16_t*)((uint32_t*)(lds + 2 * RS::BUF) + 16 * upwta_line_dwords(NWD));
+    const float inv_u = 1.0f / (float)max(100 - g.uniq, 1);
+    if constexpr (FUSE && upwta_ttab(DPL)) {
+        for (int i = tid; i < kThreshN; i += kWG) ((uint16_t*)ttab)[i] = (uint16_t)wta_thresh(i, g.uniq, inv_u);
+    }
     __syncthreads();
 
     // up+WTA (FUSE): the NP - 1 other volumes of the line's pixel, loaded one step ahead
-    constexpr int NWD = (DPL + 3) / 4;
     constexpr int NV = NP - 1;
     uint32_t vw[NV][NWD], emaskE[NWD], emaskO[NWD];
-    uint32_t* srow = (uint32_t*)(lds + 2 * RS::BUF) + j * 32 * NWD;
-    const float inv_u = 1.0f / (float)max(100 - g.uniq, 1);
+    uint32_t* srow = (uint32_t*)(lds + 2 * RS::BUF) + j * upwta_line_dwords(NWD);
     const uint32_t voff = (uint32_t)((min(max(xb + j, g.minX1), g.maxX1 - 1) - g.minX1) * g.D + (lane_act ? p * DPL : 0));
     // The set's base in a scalar pair of its own: as a part of the 16-dword kernel-argument load it
     // came from, the register allocator spilled and reloaded all 16 dwords around every step.
@@ -678,8 +725,41 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
         wta_emask<DPL, EXACT>(p, g, emaskE, emaskO);
         vload(s0);
     }
-    const uint64_t* resrow = FUSE ? uw.res + (size_t)(g.H - 1 - s0) * g.W : nullptr;   // up+WTA: row y of step s0
-    auto step = [&](int s, const uint64_t* bufc) {
+    // up+WTA: the per-pixel tail of the WTA (wta_tail) is the same in the 16 lanes of a line, so it
+    // is deferred: each step leaves the tail's inputs (best | minS << 9, sm | sp << 16, T, tot) in
+    // slot (s - s0) % 16 of the line's LDS row, and every 16 steps the tail runs once with one pixel
+    // per lane, lane p taking slot p. (Kept in registers instead, one slot per lane, the inputs cost
+    // 6 VALU per step and 11 VGPRs: the D < padded-D build spilled.) A line's slots are written and
+    // read by its own wave only, like its S slice.
+    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+    v4u* const keep = (v4u*)(srow + 32 * NWD);
+    // The tail and the result stores of steps sb .. sb + 15 (those below s1). Lane p stores its own
+    // pixel, 16 rows apart; lanes without one store past the descriptor's range, where the hardware
+    // drops them (no branch, and no trash slot: 60 of 64 lanes storing into one shared 512-B slot
+    // every step made all the frames' up+WTA waves contend on the same lines — 3 frames per launch
+    // ran 5x slower). The descriptor spans the rows of the 16 steps (the upward sweep: row
+    // H - 1 - s at step s).
+    auto flush = [&](int sb) {
+        // (the lane's p and column redefined here: left visible as loop invariants, everything below
+        // that depends on them alone is hoisted into registers that stay live over the whole sweep)
+        int pp = p, xl = xb + j;
+        asm volatile("" : "+v"(pp), "+v"(xl));
+        const v4u k = keep[pp];
+        const WtaTot t{(int)(k.x & 511u), (int)(k.x >> 9), (int)(k.y & 0xFFFFu), (int)(k.y >> 16), (int)k.z, (int)k.w};
+        const WtaPix px = wta_tail(t, g);
+        const uint64_t v = (uint64_t)(uint16_t)(px.rej ? g.invalid : px.d16) |
+                           ((uint64_t)(uint16_t)(px.rej ? -1 : px.best) << 16) | ((uint64_t)(uint16_t)px.minS << 32);
+        const int s = sb + pp;
+        const int x = xl + rx * s;
+        const int ytop = g.H - 1 - sb, ylo = max(ytop - 15, 0);       // wave-uniform
+        const bool ok = s < s1 && x >= g.minX1 && x < g.maxX1;        // s < s1 <= H: row ytop - p >= 0
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(uw.res + (size_t)ylo * g.W), 0,
+                                                                            (ytop - ylo + 1) * g.W * 8, 0x00020000);
+        typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), rr,
+                                              ok ? (uint32_t)((ytop - pp - ylo) * g.W + x) * 8u : 0x80000000u, 0, 2);
+    };
+    auto step = [&](int s, const uint64_t* bufc, bool first) {
         const int x = xb + j + rx * s;
         const bool valid = s < s1 && x >= g.minX1 && x < g.maxX1;
         const int y = ry > 0 ? s : g.H - 1 - s;
@@ -689,16 +769,16 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
         if constexpr (FUSE) {       // this step's NP - 1 costs, then the next step's loads
 #pragma unroll
             for (int jj = 0; jj < NWD; jj++) {
-                uint32_t e = 0, o = 0;
-#pragma unroll
-                for (int k = 0; k < NV; k++) {
-                    e += vw[k][jj] & 0x00FF00FFu;
-                    o += __builtin_amdgcn_perm(0u, vw[k][jj], 0x0c030c01u);
-                }
+                uint32_t e, o;
+                sum_eo<NV, NWD>(vw, jj, e, o);
                 asm("" : "+v"(e), "+v"(o));     // the sums, not 2 * NV extracted words, stay live
                 E[jj] = e;
                 O[jj] = o;
             }
+            // the previous 16 steps' tails, here where the fewest registers are live: the loaded
+            // words are summed and the next step's are not issued yet (first: the step of a loop
+            // iteration that can begin a group of 16)
+            if (first && s != s0 && ((s - s0) & 15) == 0) flush(s - 16);
         }
         // path start (first valid pixel of the line): L = C. The P2 cap of the recurrence is
         // lowered to "0" (kBase), which clamps every candidate: one select per step.
@@ -718,19 +798,11 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
             // whose temporaries they would otherwise share the register file with)
             vload(s + 1);
             __builtin_amdgcn_sched_barrier(0);
-            const WtaPix px = wta_pix16<DPL, EXACT>(E, O, p, g, inv_u, srow);
-            const uint64_t v = (uint64_t)(uint16_t)(px.rej ? g.invalid : px.d16) |
-                               ((uint64_t)(uint16_t)(px.rej ? -1 : px.best) << 16) | ((uint64_t)(uint16_t)px.minS << 32);
-            // lane 0 of each line stores its pixel; the other lanes' stores go past the row
-            // descriptor's range, where the hardware drops them (no branch, and no trash slot:
-            // 60 of 64 lanes storing into one shared 512-B slot every step made all the frames'
-            // up+WTA waves contend on the same lines — 3 frames per launch ran 5x slower)
-            // (the row base is carried from step to step: one scalar subtract, no 64-bit multiply)
-            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)resrow, 0, g.W * 8, 0x00020000);
-            resrow -= g.W;
-            typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), rr,
-                                                  (valid && p == 0) ? (uint32_t)x * 8u : 0x80000000u, 0, 2);
+            const WtaTot t = wta_tot16<DPL, EXACT>(E, O, p, [&](int minS) {
+                return upwta_ttab(DPL) ? (int)ttab[minS] : wta_thresh(minS, g.uniq, inv_u); }, srow);
+            // (all 16 lanes of the line hold the same values and write the same slot)
+            keep[(s - s0) & 15] = (v4u){(uint32_t)t.best | ((uint32_t)t.minS << 9), (uint32_t)t.sm | ((uint32_t)t.sp << 16),
+                                        (uint32_t)t.T, (uint32_t)t.tot};
         } else {
             const bool ok = valid && lane_act && !((SGM_EXP & 2) && dir == 1);
             uint8_t* const vrow = V + (size_t)min(max(y, 0), g.H - 1) * g.width1 * g.D;
@@ -742,19 +814,20 @@ __device__ __forceinline__ void p16_rows(const uint64_t* __restrict__ cL, const 
     // step s reads buf[s & 1] (holding segment s), then segment s + 1 (register set
     // (s + 1) % 4) goes to buf[(s + 1) & 1] and set s % 4 is reloaded with segment s + 4
     auto body = [&](int s, const uint64_t* bcur, uint64_t* bnext, uint64_t (&Rnext)[RS::NLOAD],
-                    uint64_t (&Rfree)[RS::NLOAD]) {
+                    uint64_t (&Rfree)[RS::NLOAD], bool first = false) {
         seg_load<DPL, LPL>(Rfree, sa, g, rx, ry, xb, min(s + 4, s1 - 1));
-        step(s, bcur);
+        step(s, bcur, first);
         seg_store<DPL, LPL>(bnext, Rnext, tid);
         __syncthreads();
     };
     for (int s = s0; s < s1; s += 4) {
         if constexpr (PRIO) lr_prio(rx != 0 ? ((s1 - s) * SGM_LRPRIO_DIAG) >> 6 : s1 - s, g.H);
-        body(s, buf0, buf1, R1, R0);
+        body(s, buf0, buf1, R1, R0, true);
         body(s + 1, buf1, buf0, R2, R1);
         body(s + 2, buf0, buf1, R3, R2);
         body(s + 3, buf1, buf0, R0, R3);
     }
+    if constexpr (FUSE) flush(s0 + ((s1 - s0 - 1) & ~15));      // the last group (s0 < s1)
 }
 
 // One work-list entry: the lines of one block of one direction of one frame (LineCfg<DPL>::HROWS
@@ -833,9 +906,10 @@ __host__ __device__ constexpr size_t wta_lds_bytes(int W) { return wta_key_bytes
 // S in packed u16 pairs by cell byte: E[j] = S of bytes (4j, 4j+2), O[j] of bytes (4j+1, 4j+3),
 // byte b holding d = p*DPL + vol_byte_d(b) (interleaved pairs); halves past D or past the
 // lane's DPL hold 0xFFFF. srow: the row's LDS slice (16 lanes x 2 * NWD dwords).
-template <int DPL, bool EXACT>
-__device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], const uint32_t (&O)[(DPL + 3) / 4],
-                                            int p, const Geom& g, float inv_u, uint32_t* srow)
+// thresh(minS): the uniqueness threshold T (wta_thresh, or a table of it).
+template <int DPL, bool EXACT, typename TF>
+__device__ __forceinline__ WtaTot wta_tot16(const uint32_t (&E)[(DPL + 3) / 4], const uint32_t (&O)[(DPL + 3) / 4],
+                                            int p, TF thresh, uint32_t* srow)
 {
     constexpr int NWD = (DPL + 3) / 4;
     // packed-key geometry: lane-local index k in the low KB bits of a 16-bit key
@@ -864,7 +938,6 @@ __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], 
     }
     km = pk_min(km, alignbit16(km, km)) & 0xFFFFu;      // lane min key (low half)
     const uint32_t kmin = row_min_u32(((km >> KB) << 9) | (uint32_t)(p * DPL + (int)(km & KMASK)));
-    WtaPix r;
     const int best = (int)(kmin & 511u);
     const int minS = (int)(kmin >> 9);
     // ---- the row's packed S slice in LDS (S[best +- 1] for subpixel and uniqueness) ----
@@ -881,23 +954,38 @@ __device__ __forceinline__ WtaPix wta_pix16(const uint32_t (&E)[(DPL + 3) / 4], 
     // max(T - S, 0) over the row exceeds its window part exactly when such a d exists. For
     // u >= 100 every d qualifies when minS > 0, and for u > 100, minS == 0 those with S > 0
     // (the count of S == 0 outside the window is the same sum with T = 1).
+    const int T = thresh(minS);
+    const uint32_t TT = (uint32_t)T * 0x10001u;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < NWD; j++) acc += pk_subs(TT, E[j]) + pk_subs(TT, O[j]);   // halves <= 2 * NWD * 2041: no carry
+    const int tot = (int)row_sum_u32(__builtin_amdgcn_sad_u16(acc, 0u, 0u));
+    return WtaTot{best, minS, sm, sp, T, tot};
+}
+
+// The uniqueness threshold T of a pixel whose minimum is minS (see wta_tot16)
+__device__ __forceinline__ int wta_thresh(int minS, int uniq, float inv_u)
+{
     int T = 0;
-    if (g.uniq < 100) {
+    if (uniq < 100) {
         if (minS > 0) {
-            const int num = minS * 100 - 1, den = 100 - g.uniq;
+            const int num = minS * 100 - 1, den = 100 - uniq;
             int q = (int)((float)num * inv_u);
             q += (q + 1) * den <= num ? 1 : 0;
             q -= q * den > num ? 1 : 0;
             T = min(q + 1, 8 * 255 + 1);      // S <= 8 * 255: keeps the u16 sums exact
         }
     } else {
-        T = (minS == 0 && g.uniq > 100) ? 1 : 0;
+        T = (minS == 0 && uniq > 100) ? 1 : 0;
     }
-    const uint32_t TT = (uint32_t)T * 0x10001u;
-    uint32_t acc = 0;
-#pragma unroll
-    for (int j = 0; j < NWD; j++) acc += pk_subs(TT, E[j]) + pk_subs(TT, O[j]);   // halves <= 2 * NWD * 2041: no carry
-    const int tot = (int)row_sum_u32(__builtin_amdgcn_sad_u16(acc, 0u, 0u));
+    return T;
+}
+
+// The per-pixel rest of the WTA: uniqueness verdict and the subpixel disparity
+__device__ __forceinline__ WtaPix wta_tail(const WtaTot& t, const Geom& g)
+{
+    const int best = t.best, minS = t.minS, sm = t.sm, sp = t.sp, T = t.T, tot = t.tot;
+    WtaPix r;
     const int win = max(T - minS, 0) + (best > 0 ? max(T - sm, 0) : 0) + (best < g.D - 1 ? max(T - sp, 0) : 0);
     int outside = tot - win;
     if (g.uniq >= 100) {
@@ -971,12 +1059,8 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
     auto sum8 = [&](const uint32_t (&v)[NP][NWD]) {
 #pragma unroll
         for (int j = 0; j < NWD; j++) {
-            uint32_t e = 0, o = 0;
-#pragma unroll
-            for (int vv = 0; vv < NP; vv++) {
-                e += v[vv][j] & 0x00FF00FFu;
-                o += __builtin_amdgcn_perm(0u, v[vv][j], 0x0c030c01u);
-            }
+            uint32_t e, o;
+            sum_eo<NP, NWD>(v, j, e, o);
             E[j] = e | emaskE[j];
             O[j] = o | emaskO[j];
         }
@@ -986,7 +1070,9 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
     sum8(nxt);
     for (int q = w; q < nq; q += 4) {
         load(min(q + 4, nq - 1), nxt);
-        const WtaPix px = wta_pix16<DPL, EXACT>(E, O, p, g, inv_u, srow);
+        // (T computed in place: a table would cost the rows 4 KB of LDS, 6 instead of 8 blocks per CU
+        // at W = 1920)
+        const WtaPix px = wta_pix16<DPL, EXACT>(E, O, p, g, [&](int minS) { return wta_thresh(minS, g.uniq, inv_u); }, srow);
         // ---- results: lane 0 of each row writes its pixel, the others hit dummy slots ----
         const int x1 = 4 * q + r;
         const bool wr = p == 0 && x1 < n;
