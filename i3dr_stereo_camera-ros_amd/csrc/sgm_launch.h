@@ -57,10 +57,12 @@ hipError_t launch_depth_points(const float* disp, size_t disp_stride, int W, int
                                size_t depth_stride, float4* points, int max_points, int* row_count, int* row_off,
                                hipStream_t st);
 
-// ocv_sgm.hip
+// ocv_cost.hip
 hipError_t launch_ocv_cost(const uint8_t* L, const uint8_t* R, size_t stride, const Geom& g, int fullDP,
                            uint8_t* planes, int16_t* bufA, int16_t* bufB, hipStream_t st);
 bool ocv_cost_takes_fused(const Geom& g);
+
+// ocv_sgm.hip (paths, WTA)
 hipError_t launch_ocv_paths(const int16_t* C, const int16_t* Csat, void* vols, size_t cells, const Geom& g,
                             int dirmask, hipStream_t st, int skipdir = -1);
 hipError_t launch_ocv_vwta(const int16_t* C, const int16_t* Csat, const void* vols, size_t cells, int ndir,

@@ -85,7 +85,7 @@ def test_fuzz_match(engine, oracle, synth, pkg, seed):
 
 
 def _ocv_fusable(h, w, kw):
-    """ocv_cost_fusable() of csrc/ocv_sgm.hip without its size default (forced below)."""
+    """ocv_cost_fusable() of csrc/ocv_cost.hip without its size default (forced below)."""
     ftzero = max(kw["prefilter_cap"], 15) | 1
     block, minD, D = kw["block_size"], kw["min_disparity"], kw["num_disparities"]
     width1 = (w + min(minD, 0)) - max(minD + D, 0)

@@ -7,7 +7,7 @@ the three known divergences as switches (oracle/sgm_oracle.c): CO
 SIMD_SAT (2), LANE_TIE (4). Here the engine runs every combination bit-exactly against the
 oracle on BASELINE configs[0] (C1), on 1920x1080, on the reference's shipped configuration
 (launch/stereo_matcher.launch:37-48) and on frames in the overflow regime, where the SIMD builds
-take the sequential saturating cost and saturating int16 paths (ocv_sgm.hip, Geom::wide).
+take the sequential saturating cost and saturating int16 paths (ocv_cost.hip, ocv_sgm.hip, Geom::wide).
 """
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""GPU parity of the fused OpenCV cost kernel (`k_ocv_cost_fused`, csrc/ocv_sgm.hip) with it forced.
+"""GPU parity of the fused OpenCV cost kernel (`k_ocv_cost_fused`, csrc/ocv_cost.hip) with it forced.
 
 The fused kernel (Birchfield-Tomasi pixel cost + vertical box + horizontal box + P2 in one pass)
 is the default on every frame of >= 10^8 cells, i.e. every production-size frame: the shipped
@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 
 def fusable(h, w, minD, D, block, cap):
-    """ocv_cost_fusable() of csrc/ocv_sgm.hip without the size default (the kernel is forced)."""
+    """ocv_cost_fusable() of csrc/ocv_cost.hip without the size default (the kernel is forced)."""
     ftzero = max(cap, 15) | 1
     sh2 = block // 2
     width1 = (w + min(minD, 0)) - max(minD + D, 0)

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Interleaved A/B of the OpenCV-mode cost stage: the two-kernel form (SGM_OCV_FUSED=0) against
 # the fused kernel at each disparity-pair width (SGM_FUSE_DPC) or band height (SGM_FUSE_ROWS), per
-# case of ocv_modes_bench.py. Build-time knobs (SGM_FUSE_RING8, _BOX_EARLY, _NB_WIDE, _WPE): variant
-# libraries from tools/build_variant.sh, timed with tools/ab_ocv.sh.
+# case of ocv_modes_bench.py. Build-time variants of the kernel (csrc/ocv_cost.hip) are made by editing
+# its named constant, built with tools/build_variant.sh and timed with tools/ab_ocv.sh.
 # Usage: tools/ab_cost.sh <rounds> <case filter> [variants...]; lines to gpurun_out/ab_cost.jsonl
 set -u
 rounds=${1:-2}; case=${2:-}; shift 2 || true
