@@ -12,6 +12,7 @@ reference's host-side interface for the hot path so tests read like the referenc
   * `parameter_callback` — generate_disparity.cpp:735-845 (cfg sanitising, matcher swap)
   * `image_cb`           — generate_disparity.cpp:635-713 (raw frames + CameraInfo -> rectified
                            images + DisparityImage, one device call in every mode)
+  * `image_cb_host`      — the same through sgm_node_frame on host arrays (`Engine.node_frame`), no torch
 
 There is no CPU fallback: if the HIP library is missing or no device is visible, matching
 fails loudly (MatcherHIPSGM.forwardMatch returns -1 exactly like the OpenCV wrapper on an
@@ -96,6 +97,7 @@ EXPORTS = [
     "sgm_default_bm_params", "sgm_set_bm_params", "sgm_get_bm_params", "sgm_check_bm_params", "sgm_debug_bm_prefilter",
     "sgm_debug_bm_sad", "sgm_set_census_paths", "sgm_get_census_paths",
     "sgm_bgr2gray", "sgm_remap_cubic_c3", "sgm_set_raw_format", "sgm_get_raw_format",
+    "sgm_node_frame", "sgm_node_frame_map_builds",
 ]
 
 
@@ -130,6 +132,41 @@ class BmParams(ctypes.Structure):
         for k, v in kw.items():
             setattr(b, k, int(v))
         return b
+
+
+class CameraInfo(ctypes.Structure):
+    """`sgm_camera_info` of include/sgm_hip.h: one camera's K, D (n_dist of 12), R (has_R), P."""
+    _fields_ = [("K", ctypes.c_double * 9), ("D", ctypes.c_double * 12), ("n_dist", ctypes.c_int),
+                ("has_R", ctypes.c_int), ("R", ctypes.c_double * 9), ("P", ctypes.c_double * 12)]
+
+    @classmethod
+    def of(cls, info):
+        """From a CameraInfo given as image_cb takes it (mapping, object or (K, D, R, P); R None: identity)."""
+        if isinstance(info, cls):
+            return info
+        K, D, R, P = _camera_info(info)
+        if len(D) > 12:
+            raise ValueError("at most 12 distortion coefficients")
+        c = cls()
+        c.K[:] = K.ravel()
+        c.D[:len(D)] = D
+        c.n_dist = len(D)
+        c.has_R = 0 if R is None else 1
+        if R is not None:
+            c.R[:] = R.ravel()
+        c.P[:] = P.ravel()
+        return c
+
+
+class NodeFrameIO(ctypes.Structure):
+    """`sgm_node_frame_io` of include/sgm_hip.h: the host buffers of one sgm_node_frame call."""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("raw_left", ctypes.c_void_p), ("raw_right", ctypes.c_void_p),
+                ("raw_stride", ctypes.c_size_t), ("width", ctypes.c_int), ("height", ctypes.c_int),
+                ("min_disparity", ctypes.c_float), ("max_disparity", ctypes.c_float),
+                ("rect_left", ctypes.c_void_p), ("rect_right", ctypes.c_void_p), ("rect_stride", ctypes.c_size_t),
+                ("disparity", ctypes.c_void_p), ("disparity_stride", ctypes.c_size_t),
+                ("depth", ctypes.c_void_p), ("depth_stride", ctypes.c_size_t), ("q5", ctypes.POINTER(ctypes.c_double)),
+                ("depth_min", ctypes.c_double), ("depth_max", ctypes.c_double)]
 
 
 _lib = None
@@ -221,6 +258,12 @@ def load_library(path=None):
     L.sgm_remap_cubic_c3.argtypes = [vp, vp, sz, ci, ci, vp, vp, sz, ci, ci, vp, sz, vp]
     L.sgm_set_raw_format.argtypes = [vp, ci, ci]
     L.sgm_get_raw_format.argtypes = [vp, P(ci), P(ci)]
+    # sgm_node_frame came the same way
+    for name in ("sgm_node_frame", "sgm_node_frame_map_builds"):
+        if not hasattr(L, name):
+            raise ImportError(f"{path}: {name} is missing: rebuild the library")
+    L.sgm_node_frame.argtypes = [vp, P(CameraInfo), P(CameraInfo), P(NodeFrameIO)]
+    L.sgm_node_frame_map_builds.argtypes = [vp]
     L.sgm_debug_bm_prefilter.argtypes = [vp, vp, ci, ci, sz, vp]
     L.sgm_debug_bm_sad.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
     _lib = L
@@ -410,6 +453,68 @@ class Engine:
         self._check(self.lib.sgm_match_device_batch_rect(self.h, arr(*d_lefts), arr(*d_rights), n, width, height,
                                                          raw_stride, rl, rr, rect_stride, arr(*d_outs), out_stride,
                                                          ctypes.c_void_p(stream) if stream else None))
+
+    def node_frame(self, left_raw, right_raw, info_left, info_right, min_disparity, max_disparity, rect_left=True,
+                   rect_right=True, disparity=None, depth=None, q5=None, depth_min=0.0, depth_max=0.0):
+        """sgm_node_frame on numpy arrays: the node's imageCb compute in one host call. left_raw /
+        right_raw: u8 H x W, or H x W x 3 after set_raw_format(3, ..); row-strided views pass without
+        a copy when both have one row stride. info_*: the cameras (CameraInfo, or what image_cb
+        takes). rect_left / rect_right: True (a new array), None / False (not wanted) or a u8 array
+        of the raw shape (row-strided, one stride for both) filled in place; disparity: None (a new
+        array) or a float32 H x W row-strided array; depth: None / False, True or such an array, with
+        q5 = (Q23, Q03, Q13, Q32, Q33). Returns (rect_left, rect_right, disparity, depth)."""
+        ch = 3 if self.get_raw_format()[0] == 3 else 1
+
+        def rows(a, dtype, isz):
+            return (a.dtype == dtype and a.strides[-1] == isz and (a.ndim == 2 or a.strides[1] == 3 * isz) and
+                    a.strides[0] >= a.shape[1] * (a.strides[1] if a.ndim == 3 else isz))
+
+        left_raw, right_raw = np.asarray(left_raw), np.asarray(right_raw)
+        if left_raw.shape != right_raw.shape or left_raw.ndim != (3 if ch == 3 else 2) or (ch == 3 and left_raw.shape[2] != 3):
+            raise ValueError("left/right must be equal-size 2-D u8 images" if ch == 1 else
+                             "left/right must be equal-size H x W x 3 u8 images (set_raw_format: 3 channels)")
+        if not (rows(left_raw, np.uint8, 1) and rows(right_raw, np.uint8, 1) and left_raw.strides[0] == right_raw.strides[0]):
+            left_raw, right_raw = np.ascontiguousarray(left_raw, np.uint8), np.ascontiguousarray(right_raw, np.uint8)
+        h, w = left_raw.shape[:2]
+        rect = [np.empty(left_raw.shape, np.uint8) if r is True else (None if r is None or r is False else r)
+                for r in (rect_left, rect_right)]
+        for r in rect:
+            if r is not None and not (r.shape == left_raw.shape and rows(r, np.uint8, 1)):
+                raise ValueError("a rectified output must be a u8 row-strided array of the raw frames' shape")
+        if rect[0] is not None and rect[1] is not None and rect[0].strides[0] != rect[1].strides[0]:
+            raise ValueError("the rectified outputs must have one common row stride")
+        if disparity is None:
+            disparity = np.empty((h, w), np.float32)
+        if depth is True:
+            depth = np.empty((h, w), np.float32)
+        elif depth is False:
+            depth = None
+        for a in (disparity, depth):
+            if a is not None and not (a.shape == (h, w) and a.ndim == 2 and rows(a, np.float32, 4) and a.strides[0] % 4 == 0):
+                raise ValueError("disparity / depth must be float32 (h, w) row-strided arrays")
+        io = NodeFrameIO()
+        io.struct_size = ctypes.sizeof(NodeFrameIO)
+        io.raw_left, io.raw_right, io.raw_stride = left_raw.ctypes.data, right_raw.ctypes.data, left_raw.strides[0]
+        io.width, io.height = w, h
+        io.min_disparity, io.max_disparity = float(min_disparity), float(max_disparity)
+        io.rect_left = rect[0].ctypes.data if rect[0] is not None else None
+        io.rect_right = rect[1].ctypes.data if rect[1] is not None else None
+        io.rect_stride = next((r.strides[0] for r in rect if r is not None), 0)
+        io.disparity, io.disparity_stride = disparity.ctypes.data, disparity.strides[0] // 4
+        qv = None
+        if depth is not None:
+            io.depth, io.depth_stride = depth.ctypes.data, depth.strides[0] // 4
+            if q5 is not None:
+                qv = (ctypes.c_double * 5)(*[float(v) for v in q5])
+                io.q5 = ctypes.cast(qv, ctypes.POINTER(ctypes.c_double))
+        io.depth_min, io.depth_max = float(depth_min), float(depth_max)
+        cl, cr = CameraInfo.of(info_left), CameraInfo.of(info_right)
+        self._check(self.lib.sgm_node_frame(self.h, ctypes.byref(cl), ctypes.byref(cr), ctypes.byref(io)))
+        return rect[0], rect[1], disparity, depth
+
+    def node_frame_map_builds(self):
+        """How often node_frame (re)built the cached rectification maps of this engine."""
+        return int(self.lib.sgm_node_frame_map_builds(self.h))
 
     def synchronize(self):
         self._check(self.lib.sgm_synchronize(self.h))
@@ -1092,3 +1197,46 @@ def image_cb(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_mi
     out = dict(image=dmat, f=f, T=T, min_disparity=float(min_disp), max_disparity=float(max_disp),
                delta_d=1.0 / 16, height=h, width=w, encoding="32FC1", step=w * 4)
     return rect[0].cpu().numpy(), rect[1].cpu().numpy(), out
+
+
+def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_min=0.0, depth_max=10.0, state=None):
+    """image_cb through the host-buffer entry point: the same arguments and return value, computed
+    by one sgm_node_frame call on the numpy arrays (Engine.node_frame), without torch. The maps are
+    cached on the matcher's engine (sgm_node_frame rebuilds them when the size or a calibration
+    changes); `state`, when given, receives the engine's build count as state["map_builds"]. The
+    engine's own rectification setting is not touched."""
+    left_raw = np.ascontiguousarray(left_raw, np.uint8)
+    right_raw = np.ascontiguousarray(right_raw, np.uint8)
+    if left_raw.shape != right_raw.shape or left_raw.ndim not in (2, 3) or (left_raw.ndim == 3 and left_raw.shape[2] != 3):
+        sys.stderr.write("Images MUST be the same resolution\n")
+        return None
+    h, w = left_raw.shape[:2]
+    ch = 3 if left_raw.ndim == 3 else 1
+    eng = matcher._engine_for()
+    params, bm = matcher.params, matcher.bm_params
+    first, second, il, ir = left_raw, right_raw, info_left, info_right
+    if matcher.interpolate:       # Q3: the right matcher on (right, left), infos and rectified outputs swapped
+        params, bm = right_matcher_params(params), right_matcher_bm_params(bm)
+        first, second, il, ir = right_raw, left_raw, info_right, info_left
+    min_disp = np.float32(T * f / depth_max)
+    with np.errstate(divide="ignore"):
+        max_disp = np.float32(T * f / depth_min) if depth_min != 0 else np.float32(np.inf)  # Q8
+    try:
+        eng.set_params(params)
+        eng.set_census_paths(matcher.census_paths)
+        eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
+        if params.mode == MODE_OCV_BM:
+            eng.set_bm_params(bm)
+        ra, rb, dmat, _ = eng.node_frame(first, second, il, ir, min_disp, max_disp)
+    except SGMError as e:      # the matcher wrappers' catch -> -1, then "Failed to compute stereo match"
+        what = "HIP StereoBM" if matcher.mode == MODE_OCV_BM else "HIP SGM"
+        sys.stderr.write("Error in %s parameters\n%s\nFailed to compute stereo match\n" % (what, e))
+        return None
+    finally:
+        if state is not None:
+            state["map_builds"] = eng.node_frame_map_builds()
+    if matcher.interpolate:
+        ra, rb = rb, ra
+    out = dict(image=dmat, f=f, T=T, min_disparity=float(min_disp), max_disparity=float(max_disp),
+               delta_d=1.0 / 16, height=h, width=w, encoding="32FC1", step=w * 4)
+    return ra, rb, out

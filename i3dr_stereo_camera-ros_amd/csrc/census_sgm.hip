@@ -1019,7 +1019,8 @@ __device__ __forceinline__ void wta_emask(int p, const Geom& g, uint32_t (&emask
 // NP: volumes summed (slots 0 .. NP-1 of the set)
 template <int DPL, bool EXACT, int NP, typename OutT = int16_t>
 __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size_t vol_bytes, const Geom& g,
-                                          OutT* __restrict__ out, size_t out_stride, int y, uint32_t* lds)
+                                          OutT* __restrict__ out, size_t out_stride, int y, uint32_t* lds,
+                                          const MsgWin& win = MsgWin{})
 {
     constexpr int NWD = (DPL + 3) / 4;            // dwords per lane per volume
     uint32_t* sl = lds;                           // 4 waves x 4 rows x 16 lanes x 2*NWD packed S dwords
@@ -1083,7 +1084,7 @@ __device__ __forceinline__ void wta_row16(const uint8_t* __restrict__ vols, size
         sum8(nxt);
     }
     R.init_key(g, tid, kWG);                      // the S slices are dead: key takes their space
-    row_finish(g, tid, kWG, R.drow, R.bst, R.mins, R.key, (int16_t*)R.mins, out + (size_t)y * out_stride);
+    row_finish(g, tid, kWG, R.drow, R.bst, R.mins, R.key, (int16_t*)R.mins, out + (size_t)y * out_stride, win);
 }
 
 // block b: row b % H of frame b / H
@@ -1111,6 +1112,18 @@ __global__ __launch_bounds__(kWG) void k_census_wta16f(WtaFrames wf, size_t vol_
 {
     extern __shared__ uint32_t lds_dyn[];
     wta_row16<DPL, EXACT, NP, float>(wf.vols[0], vol_bytes, g, wf.outf[0], wf.outf_stride, blockIdx.x, lds_dyn);
+}
+
+// The same with the rows going out as the node's DisparityImage rows (sgm_node_frame: x 1/16 and
+// the two MISSING_Z tests of k_disp_to_msg in the row store), so the frame needs no pass after
+// the WTA. win.d16 (may be null): a dense W x H device int16 image filled beside them.
+template <int DPL, bool EXACT, int NP>
+__global__ __launch_bounds__(kWG) void k_census_wta16m(WtaFrames wf, size_t vol_bytes, Geom g, MsgWin win)
+{
+    extern __shared__ uint32_t lds_dyn[];
+    if (win.d16) win.d16 += (size_t)blockIdx.x * g.W;
+    wta_row16<DPL, EXACT, NP, MsgF32>(wf.vols[0], vol_bytes, g, (MsgF32*)wf.outf[0], wf.outf_stride, blockIdx.x, lds_dyn,
+                                      win);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1445,14 +1458,16 @@ hipError_t launch_census_paths(const PathFrames& pf, size_t vol_bytes, const Geo
 // WTA + LR of the frames in wf (volumes -> disparity). np: paths summed (8, or 4: the compact
 // slots of dirs 0, 1, 6, 7).
 hipError_t launch_census_wta(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st,
-                             int np)
+                             int np, const MsgWin* msg)
 {
     with_launch_consts(g.D, np, [&](auto dpl, auto exact, auto npc) {
         constexpr int DPL = decltype(dpl)::value, NP = decltype(npc)::value;
         constexpr bool EXACT = decltype(exact)::value;
         dim3 grid(g.H * wf.n), block(kWG);
         const size_t lds = wta_lds_bytes<DPL>(g.W);
-        if (wf.outf[0])                    // one frame, float rows into a mapped host buffer
+        if (wf.outf[0] && msg)             // one frame, DisparityImage rows into a mapped host buffer
+            hipLaunchKernelGGL((k_census_wta16m<DPL, EXACT, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g, *msg);
+        else if (wf.outf[0])               // one frame, float rows into a mapped host buffer
             hipLaunchKernelGGL((k_census_wta16f<DPL, EXACT, NP>), dim3(g.H), block, lds, st, wf, vol_bytes, g);
         else
             hipLaunchKernelGGL((k_census_wta16<DPL, EXACT, NP>), grid, block, lds, st, wf, vol_bytes, g, out_stride);

@@ -3,6 +3,8 @@
 //  k_disp_to_msg   int16 ×16 disparity -> the DisparityImage float image
 //                  (generate_disparity.cpp:426-452: convertTo(..., 1/16), then
 //                  setTo(MISSING_Z) below min_disparity and above max_disparity)
+//  k_msg_tail      sgm_node_frame's tail: the same image and, from the value in registers, the
+//                  depth image, in one pass over the int16 disparity
 //  k_depth_count / k_depth_scan / k_depth_write
 //                  DisparityImage float image -> depth image + XYZRGB point list in raster
 //                  order (disparity_to_depth.cpp:127-205, Q from calc_q :62-84)
@@ -47,6 +49,28 @@ __device__ __forceinline__ bool depth_pixel(float d, int i, int j, const DepthQ&
     z = q.wz / w;
     if (!(w > 0.0f && z > 0.0f)) return false;
     return (double)z <= q.zmax && (double)z >= q.zmin;
+}
+
+// The frame tail of sgm_node_frame in one pass over the int16 disparity: the DisparityImage row
+// (k_disp_to_msg's expression and order) and, from that value in registers, the depth row
+// (depth_pixel, 0 where no point: what k_depth_count writes from the float image it reads back).
+// Either output may be null.
+__global__ __launch_bounds__(256) void k_msg_tail(const int16_t* __restrict__ disp, size_t disp_stride, int W,
+                                                  float min_disp, float max_disp, float* __restrict__ msg,
+                                                  size_t msg_stride, DepthQ q, float* __restrict__ depth,
+                                                  size_t depth_stride)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    float v = (float)disp[(size_t)y * disp_stride + x] * 0.0625f;
+    if (v < min_disp) v = kMissingZ;
+    if (v > max_disp) v = kMissingZ;
+    if (msg) msg[(size_t)y * msg_stride + x] = v;
+    if (depth) {
+        float px, py, pz;
+        const bool ok = depth_pixel(v, y, x, q, px, py, pz);
+        depth[(size_t)y * depth_stride + x] = ok ? pz : 0.0f;
+    }
 }
 
 // pass 1: depth image (0 where no point) and the number of points of every row
@@ -133,6 +157,18 @@ hipError_t launch_disp_to_msg(const int16_t* disp, size_t disp_stride, int W, in
 {
     hipLaunchKernelGGL(k_disp_to_msg, dim3((W + 255) / 256, H), dim3(256), 0, st, disp, disp_stride, W, H, min_disp,
                        max_disp, out, out_stride);
+    return hipGetLastError();
+}
+
+// qf (the five Q terms as float) is read only when depth is not null
+hipError_t launch_msg_tail(const int16_t* disp, size_t disp_stride, int W, int H, float min_disp, float max_disp,
+                           float* msg, size_t msg_stride, const float qf[5], double zmin, double zmax, float* depth,
+                           size_t depth_stride, hipStream_t st)
+{
+    DepthQ q{};
+    if (depth) q = DepthQ{qf[0], qf[1], qf[2], qf[3], qf[4], zmin, zmax};
+    hipLaunchKernelGGL(k_msg_tail, dim3((W + 255) / 256, H), dim3(256), 0, st, disp, disp_stride, W, min_disp, max_disp,
+                       msg, msg_stride, q, depth, depth_stride);
     return hipGetLastError();
 }
 

@@ -146,6 +146,9 @@ void sgm_destroy(sgm_handle* h)
         if (h->io_pin) (void)hipHostFree(h->io_pin);
         if (h->cpy) { (void)hipStreamSynchronize(h->cpy); (void)hipStreamDestroy(h->cpy); }
         if (h->cpy_ev) (void)hipEventDestroy(h->cpy_ev);
+        if (h->node_ev) (void)hipEventDestroy(h->node_ev);
+        if (h->node_maps) (void)hipFree(h->node_maps);
+        if (h->node_buf) (void)hipFree(h->node_buf);
         for (const auto& r : h->regs) (void)hipHostUnregister(r.host);
         if (h->done) (void)hipEventDestroy(h->done);
         if (h->stream) (void)hipStreamDestroy(h->stream);

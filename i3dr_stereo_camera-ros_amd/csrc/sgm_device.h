@@ -274,6 +274,14 @@ __device__ __forceinline__ void wta_batch(const int (&S)[U][DPL], int lane, cons
     drow[keep ? g.W + lane : x] = (int16_t)dv;   // rejected pixels keep the invalid value
 }
 
+// The DisparityImage float pixel as an output type of row_finish (beside int16_t and float), and
+// what its store needs: the node's disparity window and, optionally, an int16 row to fill too.
+struct MsgF32 { float v; };
+struct MsgWin {
+    float lo, hi;        // min_disparity / max_disparity of the DisparityImage
+    int16_t* d16;        // may be null
+};
+
 // Row epilogue, after every pixel of the row went through wta_batch:
 //  1. disp2 (right-view disparity, OpenCV's x-descending "strictly better" rule): for each
 //     target column x2 the pixel with the smallest minS wins, ties -> the largest x. This
@@ -284,10 +292,25 @@ __device__ __forceinline__ void wta_batch(const int (&S)[U][DPL], int lane, cons
 //     differ by more than disp12.
 //  3. store of the full row (columns outside [minX1, maxX1) stay invalid).
 // `key` needs W uint32; `d2` may alias `mins` (mins is dead after step 1). OutT = float: the
-// row goes out as the node's CV_32FC1 (every int16 is exact in float).
+// row goes out as the node's CV_32FC1 (every int16 is exact in float). OutT = MsgF32: the row
+// goes out as the node's DisparityImage row (row_store below), with the window `win`.
+template <typename OutT>
+__device__ __forceinline__ void row_store(OutT* orow, int x, int d1, const MsgWin&) { orow[x] = (OutT)d1; }
+// processDisparity's tail on one pixel, depth.hip k_disp_to_msg's expression and order: x 1/16
+// (exact), MISSING_Z below the window, then MISSING_Z above it. win.d16 (may be null): the row
+// of a device int16 copy of the image, for a depth pass that must not read the float rows back.
+__device__ __forceinline__ void row_store(MsgF32* orow, int x, int d1, const MsgWin& win)
+{
+    float v = (float)d1 * 0.0625f;
+    if (v < win.lo) v = 10000.0f;
+    if (v > win.hi) v = 10000.0f;
+    orow[x].v = v;
+    if (win.d16) win.d16[x] = (int16_t)d1;
+}
 template <typename OutT>
 __device__ __forceinline__ void row_finish(const Geom& g, int tid, int nthr, const int16_t* drow, const int16_t* bst,
-                                           const uint16_t* mins, uint32_t* key, int16_t* d2, OutT* orow)
+                                           const uint16_t* mins, uint32_t* key, int16_t* d2, OutT* orow,
+                                           const MsgWin& win = MsgWin{})
 {
     __syncthreads();
     for (int x = g.minX1 + tid; x < g.maxX1; x += nthr) {
@@ -313,7 +336,7 @@ __device__ __forceinline__ void row_finish(const Geom& g, int tid, int nthr, con
                 0 <= x_ && x_ < g.W && d2[x_] >= g.minD && abs(d2[x_] - d_) > g.disp12)
                 d1 = g.invalid;
         }
-        orow[x] = (OutT)d1;
+        row_store(orow, x, d1, win);
     }
 }
 

@@ -4,6 +4,7 @@
 //   sgm_plan.cpp      decides without touching the device: geometry, workspace layouts, knobs
 //   sgm_pipeline.cpp  the handle's resources, the frame pipelines and batch schedulers (uses plan)
 //   sgm_api.cpp       create / destroy / set / get, the match and standalone kernel entry points
+//   sgm_node.cpp      sgm_node_frame: the node's imageCb on host buffers (uses pipeline)
 //   sgm_batch_io.cpp  per-device sub-handles and the host streaming ring of sgm_match_batch
 //   sgm_tiled.cpp     the two multi-device tile modes (uses open_subs / run_on_subs of batch_io)
 //   sgm_debug.cpp     profiling and the sgm_debug_* stage entry points
@@ -102,6 +103,17 @@ struct sgm_handle {
     // host-buffer matches: the right image's copy runs on `cpy` beside the left image's census
     hipStream_t cpy = nullptr;
     hipEvent_t cpy_ev = nullptr;
+    // sgm_node_frame: the cached rectification maps (four W x H float planes: left x / y, right
+    // x / y) with the bytes of the size and calibrations they were built from, the device images of
+    // a frame (raw, rectified, int16, DisparityImage, depth) and the event that follows the launch
+    // writing the rectified images
+    float* node_maps = nullptr;
+    size_t node_maps_px = 0;
+    std::vector<unsigned char> node_key;
+    int node_builds = 0;
+    char* node_buf = nullptr;
+    size_t node_buf_size = 0;
+    hipEvent_t node_ev = nullptr;
 };
 
 namespace sgm {
@@ -195,6 +207,17 @@ struct RectOut {
     size_t stride = 0;
 };
 
+// sgm_node_frame's hooks into the census frame pipeline (one frame). rows: the final standalone
+// WTA launch writes the DisparityImage rows itself (a mapped host buffer, stride in floats, window
+// and optional int16 copy in win) and the int16 output is not written; rect_ev: recorded on the
+// stream after the launch that writes the rectified images.
+struct NodeOut {
+    float* rows = nullptr;
+    size_t stride = 0;
+    MsgWin win{};
+    hipEvent_t rect_ev = nullptr;
+};
+
 // sgm_plan.cpp
 int make_geom(const sgm_params& p, int W, int H, Geom& g, std::string& err, const sgm_bm_params* bm = nullptr);
 bool use_median(const sgm_params& p);
@@ -219,11 +242,12 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
              size_t tmp_off = 0);
 int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* dL, const uint8_t* dR, size_t stride,
                  int16_t* dOut, size_t out_stride, const std::function<hipEvent_t()>& copy_r = nullptr,
-                 float* outf = nullptr, size_t outf_stride = 0, const RectOut* raw = nullptr);
+                 float* outf = nullptr, size_t outf_stride = 0, const RectOut* raw = nullptr,
+                 hipEvent_t rect_ev = nullptr);
 int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* const* dLs,
                      const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
                      uint8_t* const* rectLs = nullptr, uint8_t* const* rectRs = nullptr, size_t rect_stride = 0,
-                     FrameHooks* hooks = nullptr);
+                     FrameHooks* hooks = nullptr, const NodeOut* node = nullptr);
 int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H, const uint8_t* const* dLs,
                   const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
                   uint8_t* const* rectLs = nullptr, uint8_t* const* rectRs = nullptr, size_t rect_stride = 0);

@@ -17,7 +17,7 @@ hipError_t launch_census_paths(const PathFrames& pf, size_t vol_bytes, const Geo
                                int n_items, hipStream_t st, const uint8_t* bnd_down = nullptr,
                                const uint8_t* bnd_up = nullptr, size_t bnd_slot = 0);
 hipError_t launch_census_wta(const WtaFrames& wf, size_t vol_bytes, const Geom& g, size_t out_stride, hipStream_t st,
-                             int np = 8);
+                             int np = 8, const MsgWin* msg = nullptr);
 hipError_t launch_census_tiles(const CensusFrames& cf, int W, int H, hipStream_t st);
 hipError_t launch_census_fused(const PathFrames& pf, const WtaFrames& wf, const CensusFrames& cf, size_t vol_bytes,
                                const Geom& g, const uint32_t* items, int n_items, size_t out_stride, bool up_wta,
@@ -56,6 +56,9 @@ hipError_t launch_depth_points(const float* disp, size_t disp_stride, int W, int
                                double zmax, const uint8_t* color, size_t color_stride, int channels, float* depth,
                                size_t depth_stride, float4* points, int max_points, int* row_count, int* row_off,
                                hipStream_t st);
+hipError_t launch_msg_tail(const int16_t* disp, size_t disp_stride, int W, int H, float min_disp, float max_disp,
+                           float* msg, size_t msg_stride, const float qf[5], double zmin, double zmax, float* depth,
+                           size_t depth_stride, hipStream_t st);
 
 // ocv_cost.hip
 hipError_t launch_ocv_cost(const uint8_t* L, const uint8_t* R, size_t stride, const Geom& g, int fullDP,

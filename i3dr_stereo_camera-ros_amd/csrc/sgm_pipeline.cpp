@@ -166,10 +166,11 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
 // writes the final rows as float to outf (a mapped host buffer, row stride outf_stride floats)
 // and dOut is not written. raw (OCV / BM modes, rectification set): dL / dR are raw frames
 // (stride = raw stride) that the k_rectify_pair pre-pass rectifies into the grey planes; *raw
-// names the frame's rectified-output images.
+// names the frame's rectified-output images, and rect_ev (may be null) is recorded after the
+// pre-pass (sgm_node_frame copies the rectified images back from there on its copy stream).
 int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* dL, const uint8_t* dR, size_t stride,
                  int16_t* dOut, size_t out_stride, const std::function<hipEvent_t()>& copy_r, float* outf,
-                 size_t outf_stride, const RectOut* raw)
+                 size_t outf_stride, const RectOut* raw, hipEvent_t rect_ev)
 {
     const sgm_params& p = h->cfg.params;
     char* ws = (char*)h->ws.base;
@@ -194,6 +195,7 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
         rec.begin("rectify", (16 + 2 * ch + 2 + ch * ((raw->L ? 1 : 0) + (raw->R ? 1 : 0))) * WH);
         HIP_TRY(sgm::launch_rectify_pair(h->rect, dL, dR, stride, ch, h->cfg.gray_set, g.W, g.H, GL, GR, raw->L,
                                          raw->R, raw->stride, st), "rectify");
+        if (rect_ev) HIP_TRY(hipEventRecord(rect_ev, st), "hipEventRecord");   // the rectified images are written
         dL = GL; dR = GR; stride = g.W;
     } else if (ch == 3 && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
         // colour frames: COLOR_BGR2GRAY of both images into the handle's grey planes, then the
@@ -308,10 +310,11 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
 // (post filters read it), so no frame's output is overwritten before its median.
 // With h->rect_on, dLs / dRs are raw images (stride = raw stride) rectified inside the census
 // (the census tiles read remap(raw)), and rectLs / rectRs (may be null) receive the
-// rectified images.
+// rectified images. node (sgm_node_frame, one frame): see NodeOut in sgm_host.h.
 int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* const* dLs,
                      const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
-                     uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride, FrameHooks* hooks)
+                     uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride, FrameHooks* hooks,
+                     const NodeOut* node)
 {
     const sgm_params& p = h->cfg.params;
     char* ws = (char*)h->ws.base;
@@ -387,6 +390,7 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     if (h->rect_on) {           // remap + census of the first group, one launch
         rec.begin("rectify+census", (census_bytes + 16 * WH) * frames_of(0));
         HIP_TRY(sgm::launch_census_tiles(census_frames(0), g.W, g.H, st), "rectify+census");
+        if (node && node->rect_ev) HIP_TRY(hipEventRecord(node->rect_ev, st), "hipEventRecord");
     } else {
         for (int f = 0; f < frames_of(0); f++) {
             rec.begin("census", census_bytes);
@@ -425,7 +429,10 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
             }
         } else if (k == ng) {
             rec.begin("wta_lr", (np * cells + 2 * WH) * frames_of(k - 1));
-            HIP_TRY(sgm::launch_census_wta(wta_frames(k - 1), l.vol_bytes, g, dst_stride, st, np), "wta");
+            sgm::WtaFrames wf = wta_frames(k - 1);
+            const bool rows = node && node->rows;     // sgm_node_frame: DisparityImage rows from this launch
+            if (rows) { wf.outf[0] = node->rows; wf.outf_stride = node->stride; }
+            HIP_TRY(sgm::launch_census_wta(wf, l.vol_bytes, g, dst_stride, st, np, rows ? &node->win : nullptr), "wta");
         } else if (ng == 1) {
             rec.begin(np == 4 ? "paths4" : "paths8", np * cells * frames_of(0));
             HIP_TRY(sgm::launch_census_paths(path_frames(0), l.vol_bytes, g, items, n_items, st), "paths");

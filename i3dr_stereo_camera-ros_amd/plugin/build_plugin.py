@@ -1,5 +1,6 @@
 """Build the OpenCV-free plugin core (hip_sgm_core.cpp) into lib/libsgm_plugin_core.so and
-its C++ test drivers lib/plugin_core_test, lib/plugin_bm_test and lib/plugin_paths_test, all linked against lib/libsgm_hip.so with g++.
+its C++ test drivers lib/plugin_core_test, lib/plugin_bm_test, lib/plugin_paths_test and
+lib/plugin_frame_test, all linked against lib/libsgm_hip.so with g++.
 (matcherHIPSGM.cpp needs OpenCV + the reference headers and is built inside the ROS tree.)"""
 import os
 import subprocess
@@ -39,6 +40,11 @@ def build():
     if _stale(paths_drv, deps + [paths_src]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
                               [paths_src, core_src, "-o", paths_drv] + link)
+    frame_src = os.path.join(HERE, "plugin_frame_test.cpp")
+    frame_drv = os.path.join(LIBDIR, "plugin_frame_test")
+    if _stale(frame_drv, deps + [frame_src]):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
+                              [frame_src, core_src, "-o", frame_drv] + link)
     return so
 
 

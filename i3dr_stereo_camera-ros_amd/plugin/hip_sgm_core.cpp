@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <string>
 
 namespace sgm_hip {
@@ -179,6 +180,69 @@ int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t
         // matcherOpenCVBlock.cpp:40 / matcherOpenCVSGBM.cpp:40 style
         std::cerr << (p.mode == SGM_MODE_OCV_BM ? "Error in HIP StereoBM parameters" : "Error in HIP SGM parameters") << std::endl
                   << err_ << " (status " << rc << ")" << std::endl;
+        return -1;
+    }
+    return 0;
+}
+
+void MatcherCore::disparityWindow(double f, double T, double depth_min, double depth_max, float* min_disp,
+                                  float* max_disp)
+{
+    *min_disp = (float)(T * f / depth_max);
+    *max_disp = depth_min != 0 ? (float)(T * f / depth_min) : std::numeric_limits<float>::infinity();   // Q8
+}
+
+int MatcherCore::mapBuilds() const { return sgm_node_frame_map_builds(handle_); }
+
+int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int w, int h, int channels,
+                         size_t raw_stride, const sgm_camera_info& info_left, const sgm_camera_info& info_right,
+                         double f, double T, double depth_min, double depth_max, uint8_t* rect_left,
+                         uint8_t* rect_right, size_t rect_stride, float* disparity, size_t disparity_stride,
+                         float* depth, size_t depth_stride, const double* q5)
+{
+    const sgm_params p = interpolate_ ? rightMatcherParams(params_) : params_;
+    const sgm_bm_params bm = interpolate_ ? rightMatcherBmParams(bm_) : bm_;
+    sgm_node_frame_io io{};
+    io.struct_size = sizeof io;
+    io.raw_left = interpolate_ ? raw_right : raw_left;       // Q3: the right matcher on (right, left)
+    io.raw_right = interpolate_ ? raw_left : raw_right;
+    io.raw_stride = raw_stride;
+    io.width = w;
+    io.height = h;
+    disparityWindow(f, T, depth_min, depth_max, &io.min_disparity, &io.max_disparity);
+    io.rect_left = interpolate_ ? rect_right : rect_left;
+    io.rect_right = interpolate_ ? rect_left : rect_right;
+    io.rect_stride = rect_stride;
+    io.disparity = disparity;
+    io.disparity_stride = disparity_stride;
+    io.depth = depth;
+    io.depth_stride = depth_stride;
+    io.q5 = q5;
+    io.depth_min = depth_min;
+    io.depth_max = depth_max;
+    int rc = SGM_OK;
+    if (!handle_) rc = sgm_create(&handle_, device_);
+    if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
+    if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
+    if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
+    // colour frames: the grey set of the OpenCV release the compat bits name (COL0_LEGACY marks 3.x)
+    if (rc == SGM_OK)
+        rc = sgm_set_raw_format(handle_, channels, (p.ocv_compat & SGM_OCV_COL0_LEGACY) ? SGM_GRAY_Y14 : SGM_GRAY_Y15);
+    if (rc == SGM_OK && keep_reg_ && disparity && h > 0) {
+        const size_t bytes = disparity_stride * sizeof(float) * (size_t)(h - 1) + (size_t)w * sizeof(float);
+        if (reg_ptr_ != (void*)disparity || reg_bytes_ != bytes) {
+            releaseOutput();
+            // not fatal: an unregistered output takes one synchronous copy
+            if (sgm_host_register(handle_, disparity, bytes) == SGM_OK) { reg_ptr_ = disparity; reg_bytes_ = bytes; }
+        }
+    }
+    if (rc == SGM_OK)
+        rc = sgm_node_frame(handle_, interpolate_ ? &info_right : &info_left, interpolate_ ? &info_left : &info_right, &io);
+    if (rc != SGM_OK) {
+        err_ = handle_ ? sgm_last_error(handle_) : "no HIP device";
+        std::cerr << (p.mode == SGM_MODE_OCV_BM ? "Error in HIP StereoBM parameters" : "Error in HIP SGM parameters") << std::endl
+                  << err_ << " (status " << rc << ")" << std::endl
+                  << "Failed to compute stereo match" << std::endl;
         return -1;
     }
     return 0;

@@ -66,6 +66,26 @@ public:
     int backwardMatch16(const uint8_t* left, const uint8_t* right, int width, int height, size_t stride,
                         int16_t* out, size_t out_stride);
 
+    // --- the node's frame -------------------------------------------------------------
+    // processDisparity's window (generate_disparity.cpp:447-450): min_disp = (float)(T*f/depth_max),
+    // max_disp = (float)(T*f/depth_min), +inf when depth_min == 0 (Q8).
+    static void disparityWindow(double f, double T, double depth_min, double depth_max, float* min_disp,
+                                float* max_disp);
+    // imageCb's compute (generate_disparity.cpp:635-713) in one sgm_node_frame call: raw u8 pair
+    // (channels 1: 8UC1, 3: 8UC3; strides in bytes) + both CameraInfos -> rectified images (either
+    // may be null), the DisparityImage float image (stride in floats) and, with q5 (sgm_depth_points'
+    // five Q terms), the depth image. The grey set of colour frames follows the compat bits (3.x:
+    // SGM_GRAY_Y14, else SGM_GRAY_Y15). With interpolation on, the right matcher's parameters run on
+    // (right, left) with the camera infos and the rectified outputs swapped (Q3). Returns 0, or -1
+    // after printing to stderr like forwardMatch.
+    int imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int width, int height, int channels,
+                size_t raw_stride, const sgm_camera_info& info_left, const sgm_camera_info& info_right, double f,
+                double T, double depth_min, double depth_max, uint8_t* rect_left, uint8_t* rect_right,
+                size_t rect_stride, float* disparity, size_t disparity_stride, float* depth = nullptr,
+                size_t depth_stride = 0, const double* q5 = nullptr);
+    // how often the frame calls (re)built the rectification maps (sgm_node_frame_map_builds)
+    int mapBuilds() const;
+
     // Keep the forwardMatch output buffer page-locked between frames (sgm_host_register) so the
     // copy-out overlaps the match; the caller must call releaseOutput() before that buffer is
     // freed or reallocated (MatcherHIPSGM: before disparity_lr.create() changes its size/type).

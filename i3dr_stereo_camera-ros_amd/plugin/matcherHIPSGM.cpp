@@ -47,6 +47,34 @@ int MatcherHIPSGM::backwardMatch()
                                (int16_t *)disparity_rl.data, disparity_rl.step / sizeof(int16_t));
 }
 
+int MatcherHIPSGM::imageCb(const cv::Mat &raw_left, const cv::Mat &raw_right, const sgm_camera_info &info_left,
+                           const sgm_camera_info &info_right, double f, double T, double depth_min, double depth_max,
+                           cv::Mat &rect_left, cv::Mat &rect_right, cv::Mat &disparity, cv::Mat *depth,
+                           const double *q5)
+{
+  const int type8UC3 = CV_8UC1 + 16;  // CV_8UC3 = CV_MAKETYPE(CV_8U, 3)
+  if ((raw_left.type() != CV_8UC1 && raw_left.type() != type8UC3) || raw_right.type() != raw_left.type() ||
+      raw_left.size() != raw_right.size() || raw_left.step != raw_right.step)
+  {
+    std::cerr << "Images MUST be the same resolution" << std::endl;
+    return -1;
+  }
+  rect_left.create(raw_left.size(), raw_left.type());
+  rect_right.create(raw_left.size(), raw_left.type());
+  if (rect_left.step != rect_right.step)
+    return -1;
+  if (disparity.size() != raw_left.size() || disparity.type() != CV_32FC1)
+    core_.releaseOutput();  // create() reallocates: unregister the old buffer before it is freed
+  disparity.create(raw_left.size(), CV_32FC1);
+  if (depth)
+    depth->create(raw_left.size(), CV_32FC1);
+  return core_.imageCb(raw_left.data, raw_right.data, raw_left.cols, raw_left.rows,
+                       raw_left.type() == type8UC3 ? 3 : 1,
+                       raw_left.step, info_left, info_right, f, T, depth_min, depth_max, rect_left.data,
+                       rect_right.data, rect_left.step, (float *)disparity.data, disparity.step / sizeof(float),
+                       depth ? (float *)depth->data : nullptr, depth ? depth->step / sizeof(float) : 0, q5);
+}
+
 void MatcherHIPSGM::setMinDisparity(int min_disparity)
 {
   core_.setMinDisparity(min_disparity);

@@ -22,6 +22,15 @@ public:
   int forwardMatch(void);
   int backwardMatch(void);
 
+  // imageCb's compute in one device call (MatcherCore::imageCb, sgm_node_frame): raw CV_8UC1 /
+  // CV_8UC3 pair + both CameraInfos -> the rectified images the node publishes and the
+  // DisparityImage float image (CV_32FC1, MISSING_Z outside [T*f/depth_max, T*f/depth_min]).
+  // depth (may be null) with q5 = {Q(2,3), Q(0,3), Q(1,3), Q(3,2), Q(3,3)}: the depth image.
+  int imageCb(const cv::Mat &raw_left, const cv::Mat &raw_right, const sgm_camera_info &info_left,
+              const sgm_camera_info &info_right, double f, double T, double depth_min, double depth_max,
+              cv::Mat &rect_left, cv::Mat &rect_right, cv::Mat &disparity, cv::Mat *depth = nullptr,
+              const double *q5 = nullptr);
+
   void setMinDisparity(int min_disparity);
   void setDisparityRange(int disparity_range);
   void setWindowSize(int window_size);

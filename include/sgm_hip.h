@@ -40,7 +40,8 @@ extern "C" {
  * sgm_set_census_paths / sgm_get_census_paths were added under version 5: they change no
  * existing struct or signature (sgm_params stays 15 ints), so the version did not move; a
  * caller that needs them checks for the symbols. The colour entry points (sgm_bgr2gray,
- * sgm_remap_cubic_c3, sgm_set_raw_format, sgm_get_raw_format) came the same way.          */
+ * sgm_remap_cubic_c3, sgm_set_raw_format, sgm_get_raw_format) came the same way, and so did
+ * sgm_node_frame / sgm_node_frame_map_builds with their two structs.                       */
 #define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
@@ -409,6 +410,58 @@ int  sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* d_raw_left
 /* The 32 x 32 x 16 int16 INTER_CUBIC weight table (entry fy*32 + fx, tap row*4 + col) the
  * remap uses. Host-only.                                                                   */
 void sgm_cubic_table(int16_t tab[16384]);
+
+/* ---- the node's frame in one host call ---------------------------------------------------- */
+/* One camera's CameraInfo, row-major doubles: K 3x3, D with n_dist = 0, 4, 5, 8 or 12 elements
+ * (as sgm_rectify_map), R 3x3 (has_R == 0: identity, R is not read), P 3x4.                  */
+typedef struct sgm_camera_info {
+    double K[9]; double D[12]; int n_dist;
+    int has_R; double R[9];
+    double P[12];
+} sgm_camera_info;
+
+/* The buffers of one frame; every image pointer is a HOST pointer. */
+typedef struct sgm_node_frame_io {
+    size_t struct_size;                       /* sizeof(sgm_node_frame_io), checked              */
+    const uint8_t* raw_left; const uint8_t* raw_right; size_t raw_stride;   /* bytes             */
+    int width, height;                        /* the node rectifies at the input size            */
+    float min_disparity, max_disparity;       /* as sgm_disparity_to_msg                         */
+    uint8_t* rect_left; uint8_t* rect_right; size_t rect_stride;  /* bytes; either may be NULL   */
+    float* disparity; size_t disparity_stride;                    /* floats; required            */
+    float* depth; size_t depth_stride; const double* q5;          /* optional; q5 as sgm_depth_points */
+    double depth_min, depth_max;
+} sgm_node_frame_io;
+
+/* The whole compute of the node's imageCb (generate_disparity.cpp:635-713) on host buffers,
+ * synchronous: both raw images (8UC1, or 8UC3 after sgm_set_raw_format) are uploaded, rectified
+ * through maps built from the two CameraInfos (rectify(), :370-386), matched in the handle's
+ * mode (sgm_set_params, sgm_set_bm_params, sgm_set_census_paths), and the outputs come back:
+ *   rect_left / rect_right  the rectified images the node publishes: sgm_remap_cubic /
+ *                           sgm_remap_cubic_c3 through sgm_rectify_map of that camera
+ *   disparity               the DisparityImage float image: sgm_disparity_to_msg of what
+ *                           sgm_match_device_batch_rect gives for the raw pair
+ *   depth                   the depth image of sgm_depth_points on `disparity` (d_points NULL)
+ * each bit for bit what those calls give. The four float maps are cached on the handle and
+ * rebuilt only when the size or any byte of K, D[0..n_dist), n_dist, has_R, R or P of either
+ * camera changes (sgm_node_frame_map_builds counts the builds); sgm_destroy frees them. The
+ * rectified images are copied back on a second stream beside the match. An output inside an
+ * sgm_host_register range goes through its mapping; in the census mode without median and
+ * speckle filter the final WTA launch then writes the `disparity` rows itself (no pass after the
+ * matcher; with `depth` it also fills a device int16 image, which one depth pass reads).
+ * Otherwise one launch after the matcher (profiling stage `msg`; sgm_stage_bytes: 2 B/px read,
+ * 4 B/px per float image written) reads the int16 disparity once and writes both float images.
+ * The caller's sgm_set_rectification state is left exactly as found, also on failure, and the
+ * call is ordered with the handle's other calls like every match.
+ * Errors: SGM_ERR_ARG for a null handle, io or required pointer, a struct_size other than
+ * sizeof(sgm_node_frame_io), a stride smaller than a row, depth without q5; sgm_rectify_map's
+ * SGM_ERR_UNSUPPORTED (n_dist) and SGM_ERR_ARG (singular P * R); then the matcher's parameter
+ * errors as at any match (a frame without a disparity window: SGM_ERR_UNSUPPORTED). All of them
+ * are decided before any output byte is written. Added under ABI version 5 (no existing struct
+ * or signature changed): callers check for the symbol.                                        */
+int  sgm_node_frame(sgm_handle* h, const sgm_camera_info* left, const sgm_camera_info* right,
+                    const sgm_node_frame_io* io);
+/* How often sgm_node_frame (re)built the handle's cached maps (0 for a null handle).          */
+int  sgm_node_frame_map_builds(const sgm_handle* h);
 
 /* ---- stage entry points (parity tests compare each stage with the CPU oracle) ----------- */
 /* 9x7 census codes of one image (host buffers; out: W x H uint64, row-major).             */
