@@ -54,6 +54,10 @@ GRAY_Y14 = 0   # OpenCV 3.2 (melodic): (c0*1868 + c1*9617 + c2*4899 + 2^13) >> 1
 GRAY_Y15 = 1   # OpenCV 4.x (noetic):  (c0*3735 + c1*19235 + c2*9798 + 2^14) >> 15, unverified against OpenCV
 GRAY_COEFFS = {GRAY_Y14: (1868, 9617, 4899, 14), GRAY_Y15: (3735, 19235, 9798, 15)}
 
+# hole filling (include/sgm_hip.h SGM_FILL_*): off, second-lowest candidate, lower median
+FILL_OFF, FILL_BACKGROUND, FILL_MEDIAN = 0, 1, 2
+FILL_NAMES = {"off": FILL_OFF, "background": FILL_BACKGROUND, "median": FILL_MEDIAN}
+
 
 def ocv_compat_from_env(default=COMPAT_MELODIC):
     """SGM_HIP_OCV_COMPAT = melodic | noetic | scalar | <bits> (the adapters read the same
@@ -86,6 +90,36 @@ def census_paths_from_env(default=8):
     return int(v)
 
 
+def fill_from_env():
+    """SGM_HIP_FILL = off | background | median[:gap[:min]] -> (mode, max_gap, min_neighbours), the
+    hole filter of the adapters (the C++ adapter core reads the same variable).
+    gap and min are 1 to 6 decimal digits (defaults 16 and 2) and are passed on as they are: a value
+    out of range fails at match time. Unset or empty: off. An unparsable value gives off and a note
+    on stderr, as hip_sgm_core.cpp does."""
+    raw = os.environ.get("SGM_HIP_FILL")
+    v = (raw or "").strip(" \t\n\v\f\r").lower()
+    if not v:
+        return (FILL_OFF, 16, 2)
+    parts = v.split(":")
+    nums = parts[1:]
+    if parts[0] not in FILL_NAMES or len(nums) > 2 or \
+            not all(n.isascii() and n.isdigit() and len(n) <= 6 for n in nums):
+        sys.stderr.write(f'SGM_HIP_FILL="{raw}" is not off | background | median[:gap[:min]]: hole filling off\n')
+        return (FILL_OFF, 16, 2)
+    return (FILL_NAMES[parts[0]], int(nums[0]) if len(nums) > 0 else 16, int(nums[1]) if len(nums) > 1 else 2)
+
+
+def fill_when_from_env():
+    """SGM_HIP_FILL_WHEN = always (default) | interp: with "interp" the node's interp flag drives the
+    hole filter (and replaces the Q3 right-view result); another value warns and means always."""
+    raw = os.environ.get("SGM_HIP_FILL_WHEN")
+    v = (raw or "").strip(" \t\n\v\f\r").lower()
+    if v in ("", "always", "interp"):
+        return v or "always"
+    sys.stderr.write(f'SGM_HIP_FILL_WHEN="{raw}" is not always | interp: using always\n')
+    return "always"
+
+
 EXPORTS = [
     "sgm_device_count", "sgm_create", "sgm_destroy", "sgm_default_params", "sgm_set_params", "sgm_get_params",
     "sgm_check_params", "sgm_match", "sgm_match_f32", "sgm_match_device", "sgm_match_device_batch", "sgm_match_batch", "sgm_match_tiled",
@@ -98,6 +132,8 @@ EXPORTS = [
     "sgm_debug_bm_sad", "sgm_set_census_paths", "sgm_get_census_paths",
     "sgm_bgr2gray", "sgm_remap_cubic_c3", "sgm_set_raw_format", "sgm_get_raw_format",
     "sgm_node_frame", "sgm_node_frame_map_builds",
+    "sgm_default_fill_params", "sgm_set_fill_params", "sgm_get_fill_params", "sgm_check_fill_params",
+    "sgm_fill_holes", "sgm_debug_fill",
 ]
 
 
@@ -132,6 +168,21 @@ class BmParams(ctypes.Structure):
         for k, v in kw.items():
             setattr(b, k, int(v))
         return b
+
+
+class FillParams(ctypes.Structure):
+    """`sgm_fill_params` of include/sgm_hip.h: the hole-filling post filter (mode FILL_*, max_gap
+    1..255, min_neighbours 1..8)."""
+    _fields_ = [("mode", ctypes.c_int), ("max_gap", ctypes.c_int), ("min_neighbours", ctypes.c_int)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def copy(self, **kw):
+        f = FillParams(self.mode, self.max_gap, self.min_neighbours)
+        for k, v in kw.items():
+            setattr(f, k, int(v))
+        return f
 
 
 class CameraInfo(ctypes.Structure):
@@ -266,6 +317,18 @@ def load_library(path=None):
     L.sgm_node_frame_map_builds.argtypes = [vp]
     L.sgm_debug_bm_prefilter.argtypes = [vp, vp, ci, ci, sz, vp]
     L.sgm_debug_bm_sad.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
+    # ... and the hole-filling entry points
+    for name in ("sgm_default_fill_params", "sgm_set_fill_params", "sgm_get_fill_params", "sgm_check_fill_params",
+                 "sgm_fill_holes", "sgm_debug_fill"):
+        if not hasattr(L, name):
+            raise ImportError(f"{path}: {name} is missing: rebuild the library")
+    L.sgm_default_fill_params.argtypes = [P(FillParams)]
+    L.sgm_default_fill_params.restype = None
+    L.sgm_set_fill_params.argtypes = [vp, P(FillParams)]
+    L.sgm_get_fill_params.argtypes = [vp, P(FillParams)]
+    L.sgm_check_fill_params.argtypes = [P(FillParams)]
+    L.sgm_fill_holes.argtypes = [vp, vp, sz, ci, ci, ci, P(FillParams), ci, ci, ci, ci, vp, sz, vp]
+    L.sgm_debug_fill.argtypes = [vp, vp, ci, ci, ci, P(FillParams), ci, ci, ci, ci]
     _lib = L
     return L
 
@@ -284,6 +347,14 @@ def default_bm_params(**kw):
     for k, v in kw.items():
         setattr(b, k, int(v))
     return b
+
+
+def default_fill_params(**kw):
+    f = FillParams()
+    load_library().sgm_default_fill_params(ctypes.byref(f))
+    for k, v in kw.items():
+        setattr(f, k, int(v))
+    return f
 
 
 def bm_geometry(params, width, height):
@@ -388,6 +459,35 @@ class Engine:
         c, g = ctypes.c_int(), ctypes.c_int()
         self._check(self.lib.sgm_get_raw_format(self.h, ctypes.byref(c), ctypes.byref(g)))
         return c.value, g.value
+
+    def set_fill_params(self, f):
+        """The hole-filling post filter of every match of this engine (FillParams; mode FILL_OFF
+        switches it off). Stored as given; bad values fail at match time."""
+        self._check(self.lib.sgm_set_fill_params(self.h, ctypes.byref(f)))
+
+    def get_fill_params(self):
+        f = FillParams()
+        self._check(self.lib.sgm_get_fill_params(self.h, ctypes.byref(f)))
+        return f
+
+    def fill_holes(self, d_src, src_stride, width, height, invalid, params, rect, d_dst, dst_stride, stream=None):
+        """sgm_fill_holes on device pointers (int16 images, strides in elements): the holes of
+        rect = (x0, y0, x1, y1) filled under `params`; asynchronous on `stream`."""
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        self._check(self.lib.sgm_fill_holes(self.h, ctypes.c_void_p(d_src), int(src_stride), int(width), int(height),
+                                            int(invalid), ctypes.byref(params), x0, y0, x1, y1,
+                                            ctypes.c_void_p(d_dst), int(dst_stride), ctypes.c_void_p(stream or 0)))
+
+    def fill(self, disp, invalid, params, rect=None):
+        """The hole filter on a host int16 image (sgm_debug_fill); rect = (x0, y0, x1, y1), default the
+        whole image. Returns the filled copy."""
+        out = np.ascontiguousarray(disp, np.int16).copy()
+        if out.ndim != 2:
+            raise ValueError("disp must be a 2-D int16 image")
+        h, w = out.shape
+        x0, y0, x1, y1 = (int(v) for v in (rect if rect is not None else (0, 0, w, h)))
+        self._check(self.lib.sgm_debug_fill(self.h, _ptr(out), w, h, int(invalid), ctypes.byref(params), x0, y0, x1, y1))
+        return out
 
     def _host_pair(self, left, right):
         """Contiguous u8 host frames of a match: H x W, or H x W x 3 once set_raw_format(3, ..) was
@@ -857,6 +957,10 @@ class MatcherHIPSGM:
     OpenCV-compatible default is MODE_SGBM = 5 directions; env SGM_HIP_MODE overrides).
     `census_paths` (census mode only): 8 or 4 aggregation paths; None reads env
     SGM_HIP_CENSUS_PATHS (default 8).
+    Hole filling (setHoleFilling, env SGM_HIP_FILL) runs after every match of the adapter. With env
+    SGM_HIP_FILL_WHEN=interp the interp flag drives it instead: setInterpolation(true) returns the
+    forward disparity filled (mode background when SGM_HIP_FILL names none), not Q3's right-view
+    image, and setInterpolation(false) returns it unfilled.
     """
 
     def __init__(self, param_file=" ", image_size=(0, 0), device=0, mode=None, census_paths=None):
@@ -876,6 +980,8 @@ class MatcherHIPSGM:
         self.device = device
         self.mode = mode
         self.census_paths = census_paths_from_env(8) if census_paths is None else int(census_paths)
+        self.fill = FillParams(*fill_from_env())
+        self.fill_when = fill_when_from_env()
         self.init()
 
     # --- AbstractStereoMatcher ----------------------------------------------------------
@@ -924,6 +1030,24 @@ class MatcherHIPSGM:
     def setInterpolation(self, enable):
         self.interpolate = bool(enable)
 
+    def setHoleFilling(self, mode, max_gap=16, min_neighbours=2):
+        """The hole filter after every match (FILL_OFF / FILL_BACKGROUND / FILL_MEDIAN); stored as
+        given, bad values fail at match time."""
+        self.fill = FillParams(int(mode), int(max_gap), int(min_neighbours))
+
+    def effective_fill(self):
+        """The filter a match runs with: the configured one, or under SGM_HIP_FILL_WHEN=interp the
+        one the interp flag selects."""
+        if self.fill_when != "interp":
+            return self.fill
+        if not self.interpolate:
+            return FillParams(FILL_OFF, self.fill.max_gap, self.fill.min_neighbours)
+        return self.fill.copy(mode=self.fill.mode if self.fill.mode != FILL_OFF else FILL_BACKGROUND)
+
+    def q3(self):
+        """interp on and not taken over by the hole filter: the right matcher's image replaces the result."""
+        return self.interpolate and self.fill_when != "interp"
+
     def setMinDisparity(self, min_disparity):
         self.min_disparity = min_disparity
         self.params.min_disparity = int(min_disparity)
@@ -969,6 +1093,7 @@ class MatcherHIPSGM:
         eng = self._engine_for()
         eng.set_params(params)
         eng.set_census_paths(self.census_paths)
+        eng.set_fill_params(self.effective_fill())
         # colour frames: COLOR_BGR2GRAY on the device, with the grey set of the OpenCV release the
         # compat bits name (COL0_LEGACY marks 3.x: Y14; otherwise 4.x: Y15)
         eng.set_raw_format(3 if np.ndim(a) == 3 else 1,
@@ -979,7 +1104,7 @@ class MatcherHIPSGM:
 
     def forwardMatch(self):
         try:
-            if self.interpolate:
+            if self.q3():
                 # Q3: the WLS output is discarded and disparity_rl (CV_16S) replaces disparity_lr
                 self.backwardMatch()
                 self.disparity_lr = self.disparity_rl.astype(np.float32)
@@ -1167,11 +1292,12 @@ def image_cb(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_mi
         ml, mr = (maps[0].data_ptr(), maps[1].data_ptr()), (maps[2].data_ptr(), maps[3].data_ptr())
         rect = torch.empty((2,) + left_raw.shape, dtype=torch.uint8, device="cuda")
         first, second, rl, rr = dl, dr, rect[0], rect[1]
-        if matcher.interpolate:
+        if matcher.q3():
             params, bm = right_matcher_params(params), right_matcher_bm_params(bm)
             first, second, rl, rr, ml, mr = dr, dl, rect[1], rect[0], mr, ml
         eng.set_params(params)
         eng.set_census_paths(matcher.census_paths)
+        eng.set_fill_params(matcher.effective_fill())
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm)
@@ -1215,7 +1341,7 @@ def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, dep
     eng = matcher._engine_for()
     params, bm = matcher.params, matcher.bm_params
     first, second, il, ir = left_raw, right_raw, info_left, info_right
-    if matcher.interpolate:       # Q3: the right matcher on (right, left), infos and rectified outputs swapped
+    if matcher.q3():              # Q3: the right matcher on (right, left), infos and rectified outputs swapped
         params, bm = right_matcher_params(params), right_matcher_bm_params(bm)
         first, second, il, ir = right_raw, left_raw, info_right, info_left
     min_disp = np.float32(T * f / depth_max)
@@ -1224,6 +1350,7 @@ def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, dep
     try:
         eng.set_params(params)
         eng.set_census_paths(matcher.census_paths)
+        eng.set_fill_params(matcher.effective_fill())
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm)
@@ -1235,7 +1362,7 @@ def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, dep
     finally:
         if state is not None:
             state["map_builds"] = eng.node_frame_map_builds()
-    if matcher.interpolate:
+    if matcher.q3():
         ra, rb = rb, ra
     out = dict(image=dmat, f=f, T=T, min_disparity=float(min_disp), max_disparity=float(max_disp),
                delta_d=1.0 / 16, height=h, width=w, encoding="32FC1", step=w * 4)

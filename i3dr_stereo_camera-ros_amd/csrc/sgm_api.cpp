@@ -81,6 +81,70 @@ int sgm_get_census_paths(const sgm_handle* h, int* paths)
     return SGM_OK;
 }
 
+void sgm_default_fill_params(sgm_fill_params* p)
+{
+    if (p) *p = kFillDefaults;
+}
+
+int sgm_set_fill_params(sgm_handle* h, const sgm_fill_params* p)
+{
+    if (!h || !p) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->cfg.fill = *p;                 // checked at match time (prepare), like every parameter
+    return SGM_OK;
+}
+
+int sgm_get_fill_params(const sgm_handle* h, sgm_fill_params* p)
+{
+    if (!h || !p) return SGM_ERR_ARG;
+    *p = h->cfg.fill;
+    return SGM_OK;
+}
+
+int sgm_check_fill_params(const sgm_fill_params* p)
+{
+    if (!p) return SGM_ERR_ARG;
+    std::string err;
+    return fill_params_status(*p, err);
+}
+
+int sgm_fill_holes(sgm_handle* h, const int16_t* d_src, size_t src_stride, int W, int H, int invalid,
+                   const sgm_fill_params* params, int x0, int y0, int x1, int y1, int16_t* d_dst, size_t dst_stride,
+                   void* stream)
+{
+    if (!h) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return fill_holes_locked(h, d_src, src_stride, W, H, invalid, params, x0, y0, x1, y1, d_dst, dst_stride, stream);
+}
+
+}  // extern "C"
+
+// sgm_fill_holes with h->mu held by the caller. The workspace only ever grows, so a caller that
+// sized it for more than the kernel's planes (sgm_debug_fill) keeps its pointers.
+int sgm::fill_holes_locked(sgm_handle* h, const int16_t* d_src, size_t src_stride, int W, int H, int invalid,
+                           const sgm_fill_params* params, int x0, int y0, int x1, int y1, int16_t* d_dst,
+                           size_t dst_stride, void* stream)
+{
+    if (!d_src || !d_dst || !params || d_src == d_dst || W <= 0 || H <= 0 || W > 32767 || H > 32767 ||
+        src_stride < (size_t)W || dst_stride < (size_t)W || x0 < 0 || x0 > x1 || x1 > W || y0 < 0 || y0 > y1 || y1 > H ||
+        invalid < -32768 || invalid > 32767)
+        return fail(h, SGM_ERR_ARG, "bad buffers, sizes or rectangle");
+    int rc = fill_params_status(*params, h->err);
+    if (rc || (rc = ensure_stream(h))) return rc;
+    // the kernel's three planes live in the workspace: ordered with the handle's other calls, and
+    // an uploaded path work list does not survive
+    if ((rc = ensure_ws(h, sgm::fill_plane_bytes(W, H)))) return rc;
+    h->items_key[0].clear();
+    h->items_key[1].clear();
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = order_after_last(h, st))) return rc;
+    HIP_TRY(sgm::launch_fill_holes(d_src, src_stride, d_dst, dst_stride, W, H, invalid, params->mode, params->max_gap,
+                                   params->min_neighbours, x0, y0, x1, y1, h->ws.base, st), "fill");
+    return mark_done(h, st);
+}
+
+extern "C" {
+
 int sgm_set_raw_format(sgm_handle* h, int channels, int gray_set)
 {
     if (!h) return SGM_ERR_ARG;

@@ -242,6 +242,25 @@ static int debug_post(sgm_handle* h, int16_t* disp, int W, int H, int which, int
 
 int sgm_debug_median3(sgm_handle* h, int16_t* disp, int W, int H) { return debug_post(h, disp, W, H, 0, 0, 0, 0); }
 
+int sgm_debug_fill(sgm_handle* h, int16_t* disp, int W, int H, int invalid, const sgm_fill_params* params, int x0,
+                   int y0, int x1, int y1)
+{
+    if (!h || !disp || !params || W <= 0 || H <= 0) return SGM_ERR_ARG;
+    const size_t WH = (size_t)W * H, img = align_up(WH * 2);
+    std::lock_guard<std::mutex> lk(h->mu);        // held to the end: the workspace stays as carved here
+    int rc = ensure_stream(h);
+    if (rc || (rc = order_after_last(h, h->stream))) return rc;
+    // the two images behind the planes that the filter takes from the workspace's start
+    if ((rc = ensure_ws(h, sgm::fill_plane_bytes(W, H) + 2 * img))) return rc;
+    int16_t* a = (int16_t*)((char*)h->ws.base + sgm::fill_plane_bytes(W, H));
+    int16_t* b = (int16_t*)((char*)a + img);
+    HIP_TRY(hipMemcpyAsync(a, disp, WH * 2, hipMemcpyHostToDevice, h->stream), "H2D");
+    if ((rc = fill_holes_locked(h, a, W, W, H, invalid, params, x0, y0, x1, y1, b, W, nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(disp, b, WH * 2, hipMemcpyDeviceToHost, h->stream), "D2H");
+    HIP_TRY(hipStreamSynchronize(h->stream), "sync");
+    return SGM_OK;
+}
+
 int sgm_debug_path_items(const sgm_params* p, int width, int height, unsigned dir_mask, int n_slots, int group,
                          int up_group, uint32_t* out, int cap)
 {

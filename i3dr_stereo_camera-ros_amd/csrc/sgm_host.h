@@ -29,6 +29,7 @@ constexpr size_t kTrashBytes = 4096;   // >= 64 lanes x 32 disparities (census_s
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 constexpr sgm_bm_params kBmDefaults = {10, 9};   // texture_threshold, prefilter_size
+constexpr sgm_fill_params kFillDefaults = {SGM_FILL_OFF, 16, 2};   // mode, max_gap, min_neighbours
 
 // What a handle matches with: the setters write it, every sub-handle family receives it whole.
 struct MatchConfig {
@@ -37,7 +38,9 @@ struct MatchConfig {
     int census_paths = 8;             // SGM_MODE_CENSUS8 only: 8, or 4 (sgm_set_census_paths)
     int raw_ch = 1;                   // sgm_set_raw_format: channels of the frames (1, or 3 = 8UC3)
     int gray_set = SGM_GRAY_Y14;      // ... and the COLOR_BGR2GRAY coefficient set used with 3
+    sgm_fill_params fill = kFillDefaults;   // sgm_set_fill_params: the hole-filling post filter
 };
+inline bool fill_on(const MatchConfig& c) { return c.fill.mode != SGM_FILL_OFF; }
 
 struct Workspace {
     void* base = nullptr;
@@ -73,6 +76,7 @@ struct sgm_handle {
     uint32_t* items_pin = nullptr; // pinned host copy of the uploaded path work list
     int items_cap = 0;
     std::string items_key[2];      // geometry + workspace each device copy (single / group) belongs to
+    std::string layout_sig;        // the workspace carve-up of the last prepared call (prepare)
     int16_t* cubic_tab = nullptr;  // device INTER_CUBIC weight table (sgm_remap_cubic), built once
     bool rect_on = false;          // sgm_set_rectification: device-match inputs are raw (rectified in the census
                                    // tiles, or by the k_rectify_pair pre-pass of the OCV / BM modes)
@@ -154,8 +158,20 @@ struct Layout {
     sgm::BmPlan bm{};                                      // bm: tiling of the fused kernel
     size_t tmp = 0, lab = 0, cnt = 0;                      // post
     size_t inL = 0, inR = 0, out = 0, outf = 0;            // host-API staging (int16 / float out)
+    // hole filling on (behind everything else, so the layout without it is unchanged): the frame
+    // before the fill (one image per frame of a group, row stride W) and the kernel's three planes
+    bool fill = false;
+    size_t fsrc = 0, fpl = 0;
     size_t total = 0;
 };
+
+// Where the post filters of a frame leave their result (and the producer writes without a
+// median): the caller's image, or with hole filling this frame's image in front of the fill.
+inline int16_t* post_image(const Layout& l, const Geom& g, char* ws, size_t frame, int16_t* dOut)
+{
+    return l.fill ? (int16_t*)(ws + l.fsrc) + frame * (size_t)g.W * g.H : dOut;
+}
+inline size_t post_stride(const Layout& l, const Geom& g, size_t out_stride) { return l.fill ? (size_t)g.W : out_stride; }
 
 // sgm_pipeline.cpp: the profiling events and stage table of a handle
 long record_event(sgm_handle* h);
@@ -224,7 +240,8 @@ bool use_median(const sgm_params& p);
 bool use_speckle(const sgm_params& p);
 int speckle_scale(int mode);
 Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group = 0, int n_cu = 0, bool rect = false);
-Layout make_post_layout(const sgm_params& p, const Geom& g);
+Layout make_post_layout(const sgm_params& p, const Geom& g, bool fill = false);
+int fill_params_status(const sgm_fill_params& f, std::string& err);
 int batch_group(int n);
 bool ocv_vwta_on(const Geom& g, int fullDP);
 int ocv_batch_lanes(int n);
@@ -252,12 +269,18 @@ int run_batch_ocv(sgm_handle* h, const Layout& l0, const Geom& g0, int W, int H,
                   const uint8_t* const* dRs, int n, size_t stride, int16_t* const* outs, size_t out_stride,
                   uint8_t* const* rectLs = nullptr, uint8_t* const* rectRs = nullptr, size_t rect_stride = 0);
 int raw_format_status(sgm_handle* h, const MatchConfig& c);
+int refuse_fill(sgm_handle* h, const char* what);
 int refuse_colour(sgm_handle* h, const char* what);
 size_t raw_bpp(const sgm_handle* h);
 int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group = 0,
             bool rect = false);
 int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, size_t stride, void* out,
                size_t out_stride, bool f32);
+
+// sgm_api.cpp: sgm_fill_holes with h->mu already held
+int fill_holes_locked(sgm_handle* h, const int16_t* d_src, size_t src_stride, int W, int H, int invalid,
+                      const sgm_fill_params* params, int x0, int y0, int x1, int y1, int16_t* d_dst,
+                      size_t dst_stride, void* stream);
 
 // sgm_batch_io.cpp
 int open_subs(sgm_handle* h, const int* devices, int n_dev, std::vector<int>& devs);

@@ -49,6 +49,12 @@ hipError_t launch_speckle(const int16_t* med, size_t mstride, int16_t* d, size_t
 hipError_t launch_fill16(int16_t* d, size_t stride, int W, int H, int v, hipStream_t st);
 hipError_t launch_to_f32(const int16_t* s, size_t ss, float* d, size_t ds, int W, int H, hipStream_t st);
 
+// fill.hip
+size_t fill_plane_bytes(int W, int H);
+hipError_t launch_fill_holes(const int16_t* src, size_t sstride, int16_t* dst, size_t dstride, int W, int H,
+                             int invalid, int mode, int G, int N, int x0, int y0, int x1, int y1, void* planes,
+                             hipStream_t st);
+
 // depth.hip
 hipError_t launch_disp_to_msg(const int16_t* disp, size_t disp_stride, int W, int H, float min_disp, float max_disp,
                               float* out, size_t out_stride, hipStream_t st);

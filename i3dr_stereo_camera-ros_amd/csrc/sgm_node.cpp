@@ -145,7 +145,7 @@ int node_frame(sgm_handle* h, const sgm_camera_info& cl, const sgm_camera_info& 
     // outputs inside a registered range go through their mapping
     char* mDisp = mapped(h, io.disparity, io.disparity_stride * 4 * (size_t)(H - 1) + (size_t)W * 4);
     char* mDepth = io.depth ? mapped(h, io.depth, io.depth_stride * 4 * (size_t)(H - 1) + (size_t)W * 4) : nullptr;
-    const bool wta_rows = census && !use_median(p) && !use_speckle(p) && mDisp;
+    const bool wta_rows = census && !use_median(p) && !use_speckle(p) && !l.fill && mDisp;
     const float qf[5] = {io.q5 ? (float)io.q5[0] : 0.f, io.q5 ? (float)io.q5[1] : 0.f, io.q5 ? (float)io.q5[2] : 0.f,
                          io.q5 ? (float)io.q5[3] : 0.f, io.q5 ? (float)io.q5[4] : 0.f};
 

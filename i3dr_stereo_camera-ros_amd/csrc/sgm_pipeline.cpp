@@ -144,6 +144,11 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
     const double WH = (double)g.W * g.H;
     const int16_t* raw = (const int16_t*)(ws + l.tmp) + tmp_off;
     const bool med = use_median(p), spk = use_speckle(p);
+    // with hole filling the filters below leave their result in this frame's image in front of it
+    int16_t* const fOut = dOut;
+    const size_t f_stride = out_stride;
+    dOut = post_image(l, g, ws, tmp_off / ((size_t)g.W * g.H), dOut);
+    out_stride = post_stride(l, g, out_stride);
     if (med && !spk) {
         rec.begin("median3", 4 * WH);
         HIP_TRY(sgm::launch_median3(raw, g.W, dOut, out_stride, g.W, g.H, h->stream), "median3");
@@ -154,6 +159,17 @@ int run_post(sgm_handle* h, const Layout& l, const Geom& g, int16_t* dOut, size_
                                     p.speckle_window_size, speckle_scale(p.mode) * p.speckle_range, (int*)(ws + l.lab),
                                     (int*)(ws + l.cnt), h->stream),
                 "speckle");
+    }
+    if (l.fill) {
+        // the rectangle: where the mode can produce a disparity (BM: also its row range)
+        const sgm_fill_params& f = h->cfg.fill;
+        const bool bm = p.mode == SGM_MODE_OCV_BM;
+        const int x0 = g.width1 > 0 ? g.minX1 : 0, x1 = g.width1 > 0 ? g.maxX1 : 0;
+        const int y0 = bm ? std::min(g.SW2, g.H) : 0, y1 = bm ? std::max(g.H - g.SW2, y0) : g.H;
+        rec.begin("fill", 4 * WH);
+        HIP_TRY(sgm::launch_fill_holes(dOut, out_stride, fOut, f_stride, g.W, g.H, g.invalid, f.mode, f.max_gap,
+                                       f.min_neighbours, x0, y0, x1, y1, ws + l.fpl, h->stream),
+                "fill");
     }
     return SGM_OK;
 }
@@ -178,8 +194,8 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
     const bool med = use_median(p);
     int16_t* tmp = (int16_t*)(ws + l.tmp);
     // the disparity producer writes to `tmp` when a median follows, else directly to dOut
-    int16_t* dst = med ? tmp : dOut;
-    const size_t dst_stride = med ? (size_t)g.W : out_stride;
+    int16_t* dst = med ? tmp : post_image(l, g, ws, 0, dOut);
+    const size_t dst_stride = med ? (size_t)g.W : post_stride(l, g, out_stride);
     const double WH = (double)g.W * g.H;
     const double cells = (double)std::max(g.width1, 0) * g.H * g.D;
     StageRec rec{h};
@@ -348,13 +364,13 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
         }
         return pf;
     };
-    size_t dst_stride = med ? (size_t)g.W : out_stride;
+    size_t dst_stride = med ? (size_t)g.W : post_stride(l, g, out_stride);
     auto wta_frames = [&](int k) {
         sgm::WtaFrames wf{};
         wf.n = frames_of(k);
         for (int f = 0; f < wf.n; f++) {
             wf.vols[f] = (const uint8_t*)(ws + l.vols[(k & 1) * G + f]);
-            wf.out[f] = med ? (int16_t*)(ws + l.tmp) + (size_t)f * g.W * g.H : outs[k * G + f];
+            wf.out[f] = med ? (int16_t*)(ws + l.tmp) + (size_t)f * g.W * g.H : post_image(l, g, ws, f, outs[k * G + f]);
             if (up) {
                 wf.cL[f] = (const uint64_t*)(ws + l.cL[code_set(k, f)]);
                 wf.cR[f] = (const uint64_t*)(ws + l.cR[code_set(k, f)]);
@@ -479,6 +495,13 @@ int refuse_colour(sgm_handle* h, const char* what)
         return fail(h, SGM_ERR_UNSUPPORTED, std::string(what) + " takes mono frames only (sgm_set_raw_format: 3 channels)");
     return SGM_OK;
 }
+// the overlap tile modes: a band filled alone would differ from the frame at its seams
+int refuse_fill(sgm_handle* h, const char* what)
+{
+    if (fill_on(h->cfg))
+        return fail(h, SGM_ERR_UNSUPPORTED, std::string(what) + " does not fill holes (sgm_set_fill_params: switch it off)");
+    return SGM_OK;
+}
 // bytes per pixel of the frames a match takes
 size_t raw_bpp(const sgm_handle* h) { return h->cfg.raw_ch == 3 ? 3 : 1; }
 
@@ -492,10 +515,16 @@ int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geo
         return fail(h, SGM_ERR_PARAM, "census paths must be 4 or 8 (sgm_set_census_paths), got " +
                                           std::to_string(c.census_paths));
     if ((rc = raw_format_status(h, c))) return rc;
+    if ((rc = fill_params_status(c.fill, h->err))) return rc;
     if ((rc = ensure_stream(h))) return rc;
     l = make_layout(c, g, host_io, group, h->n_cu, rect);
-    // the uploaded path work list lives in the workspace: any other use of it invalidates it
-    if (c.params.mode != SGM_MODE_CENSUS8) { h->items_key[0].clear(); h->items_key[1].clear(); }
+    // the uploaded path work lists live in the workspace: any other use of it invalidates them, also
+    // a census call that carves it differently (a single frame after a pipelined batch of the same
+    // geometry finds its list's offset inside the batch's second volume set)
+    char sig[128];
+    snprintf(sig, sizeof sig, "%zu %zu %zu %d %d", l.total, l.items[0], l.items[1], l.group, (int)l.up_wta);
+    if (c.params.mode != SGM_MODE_CENSUS8 || h->layout_sig != sig) { h->items_key[0].clear(); h->items_key[1].clear(); }
+    h->layout_sig = sig;
     return ensure_ws(h, l.total);
 }
 
@@ -615,7 +644,7 @@ int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, 
     // f32 output that is the WTA's own (census, no median / speckles) into a registered, mapped
     // host buffer: the WTA writes the float rows there itself (no to-float pass, no copy back)
     float* outf = nullptr;
-    if (f32 && census && !use_median(p) && !use_speckle(p)) {
+    if (f32 && census && !use_median(p) && !use_speckle(p) && !l.fill) {
         const size_t need = out_stride * 4 * (size_t)(H - 1) + (size_t)W * 4;
         for (const auto& r : h->regs)
             if (r.dev && (char*)out >= r.host && (char*)out + need <= r.host + r.bytes) {

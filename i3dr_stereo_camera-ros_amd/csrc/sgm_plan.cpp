@@ -205,12 +205,17 @@ Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group,
     if (p.speckle_window_size > 0) { l.lab = take(WH * 4); l.cnt = take(WH * 4); }
     if ((ch == 3 || rect) && p.mode != SGM_MODE_CENSUS8) { l.grayL = take(WH); l.grayR = take(WH); }
     if (host_io) { l.inL = take(WH * ch); l.inR = take(WH * ch); l.out = take(WH * 2); l.outf = take(WH * 4); }
+    if (fill_on(c)) {
+        l.fill = true;
+        l.fsrc = take(WH * 2 * (size_t)std::max(group, 1));
+        l.fpl = take(sgm::fill_plane_bytes(g.W, g.H));
+    }
     l.total = off;
     return l;
 }
 
 // Post-filter workspace of the assembled frame on the primary handle.
-Layout make_post_layout(const sgm_params& p, const Geom& g)
+Layout make_post_layout(const sgm_params& p, const Geom& g, bool fill)
 {
     Layout l;
     size_t off = 0;
@@ -219,8 +224,33 @@ Layout make_post_layout(const sgm_params& p, const Geom& g)
     l.tmp = take(WH * 2);
     l.out = take(WH * 2);
     if (p.speckle_window_size > 0) { l.lab = take(WH * 4); l.cnt = take(WH * 4); }
+    if (fill) {
+        l.fill = true;
+        l.fsrc = take(WH * 2);
+        l.fpl = take(sgm::fill_plane_bytes(g.W, g.H));
+    }
     l.total = off;
     return l;
+}
+
+// sgm_set_fill_params stores anything; with a mode other than OFF a match (and sgm_fill_holes)
+// needs a known mode, a gap of 1..255 and 1..8 neighbours
+int fill_params_status(const sgm_fill_params& f, std::string& err)
+{
+    if (f.mode == SGM_FILL_OFF) return SGM_OK;
+    if (f.mode != SGM_FILL_BACKGROUND && f.mode != SGM_FILL_MEDIAN) {
+        err = "hole filling: unknown mode " + std::to_string(f.mode);
+        return SGM_ERR_PARAM;
+    }
+    if (f.max_gap < 1 || f.max_gap > 255) {
+        err = "hole filling: max_gap must be within 1..255, got " + std::to_string(f.max_gap);
+        return SGM_ERR_PARAM;
+    }
+    if (f.min_neighbours < 1 || f.min_neighbours > 8) {
+        err = "hole filling: min_neighbours must be within 1..8, got " + std::to_string(f.min_neighbours);
+        return SGM_ERR_PARAM;
+    }
+    return SGM_OK;
 }
 
 // OpenCV modes: the vertical direction of the last group fused with the WTA (k_ocv_vwta)

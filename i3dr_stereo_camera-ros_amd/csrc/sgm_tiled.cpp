@@ -53,6 +53,7 @@ int sgm_match_tiled(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
     if (int rf = refuse_colour(h, "sgm_match_tiled")) return rf;
+    if (int rf = refuse_fill(h, "sgm_match_tiled")) return rf;
     n_bands = std::min(n_bands, H);
     std::vector<int> devs;
     int rc = open_subs(h, devices, n_dev, devs);
@@ -115,6 +116,7 @@ extern "C" int sgm_match_tiled_device(sgm_handle* h, const uint8_t* dL, const ui
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
     if (int rf = refuse_colour(h, "sgm_match_tiled_device")) return rf;
+    if (int rf = refuse_fill(h, "sgm_match_tiled_device")) return rf;
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "the tile mode takes rectified images");
     n_bands = std::min(n_bands, H);
     std::vector<int> devs;
@@ -246,7 +248,7 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
     const sgm_params& p = h->cfg.params;
     Geom gf;
     int rc = make_geom(p, W, H, gf, h->err);
-    if (rc) return rc;
+    if (rc || (rc = fill_params_status(h->cfg.fill, h->err))) return rc;
     if (p.mode != SGM_MODE_CENSUS8) return fail(h, SGM_ERR_UNSUPPORTED, "the exact tile mode runs in the census mode");
     // the seam exchange carries three directions per sweep family (bnd_slot_of): 8 paths only
     if (h->cfg.census_paths != 8)
@@ -275,12 +277,12 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
         enable_peer(h->bands[b]->device, h->device);
     }
     if ((rc = ensure_stream(h))) return rc;
-    const Layout pl = make_post_layout(p, gf);
+    const Layout pl = make_post_layout(p, gf, fill_on(h->cfg));
     if ((rc = ensure_ws(h, pl.total))) return rc;
     if ((rc = ensure_pin(h, (size_t)W * H * 2))) return rc;
     const bool med = use_median(p);
     char* pws = (char*)h->ws.base;
-    int16_t* frame_raw = (int16_t*)(pws + (med ? pl.tmp : pl.out));
+    int16_t* frame_raw = med ? (int16_t*)(pws + pl.tmp) : post_image(pl, gf, pws, 0, (int16_t*)(pws + pl.out));
     const size_t cells_row = (size_t)std::max(gf.width1, 0) * gf.D;
 
     auto ws = [&](int b, size_t off) { return (char*)h->bands[b]->ws.base + off; };

@@ -7,6 +7,7 @@
 #include <iostream>
 #include <limits>
 #include <string>
+#include <vector>
 
 namespace sgm_hip {
 
@@ -61,9 +62,71 @@ int census_paths_from_env(int fallback)
     return (int)n;
 }
 
+static std::string trimmed_lower(const char* e)
+{
+    std::string v(e);
+    while (!v.empty() && std::isspace((unsigned char)v.back())) v.pop_back();
+    size_t b = 0;
+    while (b < v.size() && std::isspace((unsigned char)v[b])) b++;
+    v = v.substr(b);
+    for (char& c : v) c = (char)std::tolower((unsigned char)c);
+    return v;
+}
+
+// SGM_HIP_FILL = off | background | median[:gap[:min]]: the hole filter of the adapter
+// (sgm_set_fill_params). Case and surrounding blanks are ignored; gap and min are 1 to 6 decimal
+// digits (defaults 16 and 2) and are passed on as they are (a value out of range fails at match
+// time). Unset or blank: off. An unparsable value gives off and a note on stderr (the Python
+// mirror's fill_from_env does the same).
+sgm_fill_params fill_from_env()
+{
+    sgm_fill_params off;
+    sgm_default_fill_params(&off);
+    const char* e = std::getenv("SGM_HIP_FILL");
+    if (!e) return off;
+    const std::string v = trimmed_lower(e);
+    if (v.empty()) return off;
+    std::vector<std::string> parts(1);
+    for (char c : v) {
+        if (c == ':') parts.emplace_back();
+        else parts.back() += c;
+    }
+    sgm_fill_params f = off;
+    bool ok = parts.size() <= 3;
+    if (parts[0] == "off") f.mode = SGM_FILL_OFF;
+    else if (parts[0] == "background") f.mode = SGM_FILL_BACKGROUND;
+    else if (parts[0] == "median") f.mode = SGM_FILL_MEDIAN;
+    else ok = false;
+    for (size_t i = 1; ok && i < parts.size(); i++) {
+        const std::string& n = parts[i];
+        ok = !n.empty() && n.size() <= 6;
+        for (char c : n) ok = ok && c >= '0' && c <= '9';
+        if (ok) (i == 1 ? f.max_gap : f.min_neighbours) = std::atoi(n.c_str());
+    }
+    if (!ok) {
+        std::cerr << "SGM_HIP_FILL=\"" << e << "\" is not off | background | median[:gap[:min]]: hole filling off"
+                  << std::endl;
+        return off;
+    }
+    return f;
+}
+
+bool fill_when_interp_from_env()
+{
+    const char* e = std::getenv("SGM_HIP_FILL_WHEN");
+    if (!e) return false;
+    const std::string v = trimmed_lower(e);
+    if (v.empty() || v == "always") return false;
+    if (v == "interp") return true;
+    std::cerr << "SGM_HIP_FILL_WHEN=\"" << e << "\" is not always | interp: using always" << std::endl;
+    return false;
+}
+
 MatcherCore::MatcherCore(int device, int mode) : device_(device)
 {
     census_paths_ = census_paths_from_env(8);
+    fill_ = fill_from_env();
+    fill_when_interp_ = fill_when_interp_from_env();
     if (mode < 0) {
         const char* env = std::getenv("SGM_HIP_MODE");
         mode = env ? std::atoi(env) : SGM_MODE_OCV_SGBM5;
@@ -130,6 +193,16 @@ void MatcherCore::setInterpolation(bool e) { interpolate_ = e; }
 void MatcherCore::setMode(int m) { params_.mode = m; }
 void MatcherCore::setOcvCompat(int bits) { params_.ocv_compat = bits; }
 void MatcherCore::setCensusPaths(int paths) { census_paths_ = paths; }
+void MatcherCore::setHoleFilling(int mode, int max_gap, int min_neighbours) { fill_ = sgm_fill_params{mode, max_gap, min_neighbours}; }
+void MatcherCore::setFillWhenInterp(bool interp) { fill_when_interp_ = interp; }
+sgm_fill_params MatcherCore::effectiveFill() const
+{
+    sgm_fill_params f = fill_;
+    if (!fill_when_interp_) return f;
+    if (!interpolate_) f.mode = SGM_FILL_OFF;
+    else if (f.mode == SGM_FILL_OFF) f.mode = SGM_FILL_BACKGROUND;
+    return f;
+}
 void MatcherCore::setTextureThreshold(int t) { bm_.texture_threshold = t; }
 void MatcherCore::setPreFilterSize(int s) { bm_.prefilter_size = s; }
 
@@ -164,6 +237,8 @@ int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
     if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
     if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
+    const sgm_fill_params fill = effectiveFill();
+    if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
     if (rc == SGM_OK && keep_reg_ && outf) {
         const size_t bytes = out_stride * sizeof(float) * (size_t)(h - 1) + (size_t)w * sizeof(float);
         if (reg_ptr_ != (void*)outf || reg_bytes_ != bytes) {
@@ -200,18 +275,20 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
                          uint8_t* rect_right, size_t rect_stride, float* disparity, size_t disparity_stride,
                          float* depth, size_t depth_stride, const double* q5)
 {
-    const sgm_params p = interpolate_ ? rightMatcherParams(params_) : params_;
-    const sgm_bm_params bm = interpolate_ ? rightMatcherBmParams(bm_) : bm_;
+    const bool q3 = this->q3();      // interp on and not taken over by the hole filter
+    const sgm_params p = q3 ? rightMatcherParams(params_) : params_;
+    const sgm_bm_params bm = q3 ? rightMatcherBmParams(bm_) : bm_;
+    const sgm_fill_params fill = effectiveFill();
     sgm_node_frame_io io{};
     io.struct_size = sizeof io;
-    io.raw_left = interpolate_ ? raw_right : raw_left;       // Q3: the right matcher on (right, left)
-    io.raw_right = interpolate_ ? raw_left : raw_right;
+    io.raw_left = q3 ? raw_right : raw_left;       // Q3: the right matcher on (right, left)
+    io.raw_right = q3 ? raw_left : raw_right;
     io.raw_stride = raw_stride;
     io.width = w;
     io.height = h;
     disparityWindow(f, T, depth_min, depth_max, &io.min_disparity, &io.max_disparity);
-    io.rect_left = interpolate_ ? rect_right : rect_left;
-    io.rect_right = interpolate_ ? rect_left : rect_right;
+    io.rect_left = q3 ? rect_right : rect_left;
+    io.rect_right = q3 ? rect_left : rect_right;
     io.rect_stride = rect_stride;
     io.disparity = disparity;
     io.disparity_stride = disparity_stride;
@@ -225,6 +302,7 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
     if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
     if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
+    if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
     // colour frames: the grey set of the OpenCV release the compat bits name (COL0_LEGACY marks 3.x)
     if (rc == SGM_OK)
         rc = sgm_set_raw_format(handle_, channels, (p.ocv_compat & SGM_OCV_COL0_LEGACY) ? SGM_GRAY_Y14 : SGM_GRAY_Y15);
@@ -237,7 +315,7 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
         }
     }
     if (rc == SGM_OK)
-        rc = sgm_node_frame(handle_, interpolate_ ? &info_right : &info_left, interpolate_ ? &info_left : &info_right, &io);
+        rc = sgm_node_frame(handle_, q3 ? &info_right : &info_left, q3 ? &info_left : &info_right, &io);
     if (rc != SGM_OK) {
         err_ = handle_ ? sgm_last_error(handle_) : "no HIP device";
         std::cerr << (p.mode == SGM_MODE_OCV_BM ? "Error in HIP StereoBM parameters" : "Error in HIP SGM parameters") << std::endl
@@ -251,7 +329,7 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
 int MatcherCore::forwardMatch(const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, float* out,
                               size_t out_stride)
 {
-    if (interpolate_)  // Q3: WLS output discarded, right-view disparity returned
+    if (q3())  // Q3: WLS output discarded, right-view disparity returned
         return backwardMatch(left, right, w, h, stride, out, out_stride);
     return run(params_, bm_, left, right, w, h, stride, out, nullptr, out_stride);
 }

@@ -20,6 +20,11 @@ namespace sgm_hip {
 int ocv_compat_from_env(int fallback);
 // SGM_HIP_CENSUS_PATHS (4 | 8, any integer is passed on), else `fallback`
 int census_paths_from_env(int fallback);
+// SGM_HIP_FILL (off | background | median[:gap[:min]]; gap and min: 1 to 6 digits, defaults 16 and
+// 2, passed on as they are); unset, blank or unparsable (with a note on stderr): off
+sgm_fill_params fill_from_env();
+// SGM_HIP_FILL_WHEN (always | interp): true for interp; anything else (with a note) is always
+bool fill_when_interp_from_env();
 
 class MatcherCore {
 public:
@@ -48,6 +53,15 @@ public:
     // SGM_MODE_CENSUS8 only: 8 or 4 aggregation paths (sgm_set_census_paths; default: the
     // SGM_HIP_CENSUS_PATHS env var, else 8). Forward and backward matches both use it.
     void setCensusPaths(int paths);
+    // The hole filter after every match (sgm_set_fill_params; default: the SGM_HIP_FILL env var,
+    // else off). Stored as given: bad values fail at match time. With SGM_HIP_FILL_WHEN=interp the
+    // interp flag drives it instead: setInterpolation(true) returns the forward disparity filled
+    // (mode background when none is configured) in place of Q3's right-view image, in forwardMatch
+    // and in imageCb, and setInterpolation(false) returns it unfilled.
+    void setHoleFilling(int mode, int max_gap = 16, int min_neighbours = 2);
+    void setFillWhenInterp(bool interp);
+    sgm_fill_params effectiveFill() const;
+    bool q3() const { return interpolate_ && !fill_when_interp_; }
     // cv::StereoBM only (SGM_MODE_OCV_BM); stored but unused in the other modes, where the
     // reference's matchers ignore them too (matcherOpenCVSGBM.h:31-34)
     void setTextureThreshold(int threshold);
@@ -97,6 +111,7 @@ public:
     bool interpolation() const { return interpolate_; }
     int disparityRange() const { return params_.num_disparities; }
     int censusPaths() const { return census_paths_; }
+    const sgm_fill_params& holeFilling() const { return fill_; }
     const std::string& lastError() const { return err_; }
     // SGBM modes: cv::ximgproc::createRightMatcher of a StereoSGBM. BM mode: of a StereoBM —
     // minD' = -(minD + D) + 1, same D and window, uniqueness 0, no speckle filter, and (through
@@ -113,6 +128,8 @@ private:
     sgm_params params_{};
     sgm_bm_params bm_{};
     int census_paths_ = 8;
+    sgm_fill_params fill_{};
+    bool fill_when_interp_ = false;
     bool interpolate_ = false;
     bool keep_reg_ = false;
     void* reg_ptr_ = nullptr;        // the registered output range

@@ -18,7 +18,7 @@ int MatcherHIPSGM::forwardMatch()
     std::cerr << "Error in HIP SGM parameters" << std::endl << "expects equal-size CV_8UC1 images" << std::endl;
     return -1;
   }
-  if (interpolate)
+  if (core_.q3())
   {
     // Q3 (matcherOpenCVSGBM.cpp:22-33): the WLS output is discarded and the right-view
     // disparity (CV_16S in disparity_rl) replaces disparity_lr
@@ -102,6 +102,11 @@ void MatcherHIPSGM::setP2(float p2) { core_.setP2(p2); }
 void MatcherHIPSGM::setPreFilterCap(int cap) { core_.setPreFilterCap(cap); }
 void MatcherHIPSGM::setTextureThreshold(int threshold) { core_.setTextureThreshold(threshold); }
 void MatcherHIPSGM::setPreFilterSize(int size) { core_.setPreFilterSize(size); }
+
+void MatcherHIPSGM::setHoleFilling(int mode, int max_gap, int min_neighbours)
+{
+  core_.setHoleFilling(mode, max_gap, min_neighbours);
+}
 
 void MatcherHIPSGM::setInterpolation(bool enable)
 {

@@ -42,6 +42,10 @@ public:
   void setDisp12MaxDiff(int diff);
   void setInterpolation(bool enable);
   void setPreFilterCap(int cap);
+  // The hole filter after every match (SGM_FILL_*; default: env SGM_HIP_FILL, else off). With env
+  // SGM_HIP_FILL_WHEN=interp, setInterpolation drives it in place of the Q3 right-view result
+  // (hip_sgm_core.h setHoleFilling).
+  void setHoleFilling(int mode, int max_gap = 16, int min_neighbours = 2);
 
   // cv::StereoBM parameters: used in BM mode, ignored by the SGM modes (matcherOpenCVSGBM.h:31-34)
   void setTextureThreshold(int threshold);

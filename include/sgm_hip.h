@@ -173,6 +173,60 @@ int  sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p);
 int  sgm_set_census_paths(sgm_handle* h, int paths);
 int  sgm_get_census_paths(const sgm_handle* h, int* paths);
 
+/* ---- hole filling ------------------------------------------------------------------------- */
+/* The post filter behind the node's `interp` knob (cfg/i3DR_Disparity.cfg:39, "will smooth
+ * holes"): a bounded 8-direction nearest-valid interpolation of the final int16 disparity, run
+ * after median and speckle filter (profiling stage `fill`, last of the post filters;
+ * sgm_stage_bytes: 2 B/px read + 2 B/px written). Specified by this project (the I3DR matcher's
+ * interpolator is closed, and the OpenCV matchers' WLS result never reaches the node's output,
+ * SURVEY Q3); tests/fill_reference.py is the executable statement. Off by default.
+ *   - invalid = (min_disparity - 1) * 16. A hole is a pixel of the fill rectangle that equals
+ *     invalid; every other pixel is copied.
+ *   - each of the 8 directions (left, right, up, down and the four diagonals, one pixel on both
+ *     axes per step) contributes at most one candidate: the pixel at the smallest k in
+ *     1..max_gap steps that lies inside the image and is not invalid. Candidates may lie outside
+ *     the rectangle and are always read from the input, never from a filled pixel, so the result
+ *     does not depend on any processing order.
+ *   - with n candidates sorted v_0 <= .. <= v_{n-1}: n < min_neighbours leaves the pixel
+ *     invalid; SGM_FILL_BACKGROUND takes v_1 (v_0 when n == 1): the second-lowest value prefers
+ *     the background and tolerates one outlier; SGM_FILL_MEDIAN takes the lower median
+ *     v_{(n-1)/2}. SGM_FILL_OFF is a plain copy.
+ *   - inside a match the rectangle is the region where the mode can produce a disparity:
+ *     columns [max(maxD, 0), W + min(minD, 0)) and all rows for the SGBM, HH and census modes;
+ *     columns [X0, X1) of sgm_debug_bm_sad and rows [w/2, H - w/2) for BM. A frame without a
+ *     disparity window stays all invalid.
+ * Like every setter sgm_set_fill_params stores any value; with a mode other than SGM_FILL_OFF,
+ * a mode that is not BACKGROUND or MEDIAN, max_gap outside 1..255 or min_neighbours outside 1..8
+ * is SGM_ERR_PARAM at match time. Honoured by sgm_match, sgm_match_f32, sgm_match_device,
+ * sgm_match_device_batch[_rect], sgm_match_batch, sgm_node_frame (disparity and depth) and
+ * sgm_match_tiled_exact (its post filters run on the assembled frame); sub-handles inherit it.
+ * sgm_match_tiled and sgm_match_tiled_device return SGM_ERR_UNSUPPORTED while it is on: filling
+ * band by band would differ at the seams. While it is on, the two "the WTA writes the float rows
+ * itself" shortcuts (sgm_match_f32, sgm_node_frame) are not taken. Added under ABI version 5
+ * (no existing struct or signature changed): callers check for the symbols.                   */
+#define SGM_FILL_OFF         0
+#define SGM_FILL_BACKGROUND  1
+#define SGM_FILL_MEDIAN      2
+typedef struct sgm_fill_params {
+    int mode;                 /* SGM_FILL_*                                                    */
+    int max_gap;              /* G: the farthest step a candidate may lie away, 1..255         */
+    int min_neighbours;       /* N: candidates a hole needs to be filled, 1..8                 */
+} sgm_fill_params;
+/* {SGM_FILL_OFF, 16, 2} */
+void sgm_default_fill_params(sgm_fill_params* p);
+int  sgm_set_fill_params(sgm_handle* h, const sgm_fill_params* p);
+int  sgm_get_fill_params(const sgm_handle* h, sgm_fill_params* p);
+/* Validate fill parameters without a handle (0 = a match would accept them). Host-only.       */
+int  sgm_check_fill_params(const sgm_fill_params* p);
+/* The filter alone on device buffers, asynchronous on `stream` (NULL = the handle's stream) like
+ * sgm_disparity_to_msg: d_src -> d_dst (width x height int16, strides in elements), holes of
+ * [x0, x1) x [y0, y1) (0 <= x0 <= x1 <= width, 0 <= y0 <= y1 <= height) filled under `params`
+ * (validated as above; the handle's own fill parameters are not used). d_dst == d_src is
+ * SGM_ERR_ARG. It uses the handle's workspace, so it is ordered with the handle's other calls. */
+int  sgm_fill_holes(sgm_handle* h, const int16_t* d_src, size_t src_stride, int width, int height, int invalid,
+                    const sgm_fill_params* params, int x0, int y0, int x1, int y1, int16_t* d_dst,
+                    size_t dst_stride, void* stream);
+
 /* ---- colour frames ---------------------------------------------------------------------- */
 /* The node accepts colour cameras: imageCb rectifies whatever encoding arrives
  * (generate_disparity.cpp:651-652, :674-675) and processDisparity converts both rectified images
@@ -262,7 +316,9 @@ int  sgm_match_batch(sgm_handle* h, const uint8_t* const* lefts, const uint8_t* 
  * "single huge frame" in overlap mode: each band is matched on its rows extended by `halo`
  * rows above and below, and only its own rows are kept. No path state crosses bands, so
  * pixels near band seams can differ from the full-frame result (the tests report the
- * disagreement); n_bands = 1 is exactly sgm_match. Host buffers; synchronous.          */
+ * disagreement); n_bands = 1 is exactly sgm_match. Host buffers; synchronous. With hole
+ * filling on (sgm_set_fill_params) this call and sgm_match_tiled_device return
+ * SGM_ERR_UNSUPPORTED: a band filled alone would differ from the frame at its seams.     */
 int  sgm_match_tiled(sgm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
                      size_t stride, int16_t* disp, size_t out_stride, int n_bands, int halo,
                      const int* devices, int n_dev);
@@ -497,6 +553,9 @@ int  sgm_debug_path_items(const sgm_params* p, int width, int height, unsigned d
 int  sgm_debug_median3(sgm_handle* h, int16_t* disp, int width, int height);
 int  sgm_debug_speckle(sgm_handle* h, int16_t* disp, int width, int height,
                        int new_val, int max_size, int max_diff);
+/* sgm_fill_holes on a host int16 image, in place; synchronous.                             */
+int  sgm_debug_fill(sgm_handle* h, int16_t* disp, int width, int height, int invalid,
+                    const sgm_fill_params* params, int x0, int y0, int x1, int y1);
 
 #ifdef __cplusplus
 }
