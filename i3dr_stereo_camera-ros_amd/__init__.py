@@ -90,6 +90,41 @@ def census_paths_from_env(default=8):
     return int(v)
 
 
+CENSUS_WINDOW_DEFAULT = (9, 7, 1)
+
+
+def census_window_from_size(size):
+    """The census window of a correlation_window_size slider value (sgm_census_window_from_size,
+    the one table): (taps_x, taps_y, step)."""
+    s = int(size) | 1
+    if s <= 3:
+        return (3, 3, 1)
+    if s <= 9:
+        return {5: (5, 5, 1), 7: (7, 7, 1), 9: (9, 7, 1)}[s]
+    return (7, 7, 2) if s <= 13 else (9, 7, 2)
+
+
+def census_window_from_env():
+    """SGM_HIP_CENSUS_WINDOW = <tx>x<ty>[/<step>] | cfg (the C++ adapter core reads the same variable,
+    INTEGRATION.md §10). Returns (window, follow_cfg): unset or empty: the default 9x7 window;
+    "7x7" or "9x7/2": that window, passed on as it is (an invalid one fails at match time), each
+    number 1 to 6 decimal digits; "cfg": setWindowSize drives the window through
+    census_window_from_size. An unparsable value warns and keeps the default."""
+    raw = os.environ.get("SGM_HIP_CENSUS_WINDOW")
+    v = (raw or "").strip(" \t\n\v\f\r").lower()
+    if not v:
+        return CENSUS_WINDOW_DEFAULT, False
+    if v == "cfg":
+        return CENSUS_WINDOW_DEFAULT, True
+    size, _, step = v.partition("/")
+    tx, x, ty = size.partition("x")
+    nums = [tx, ty] + ([step] if "/" in v else [])
+    if not x or not all(n.isascii() and n.isdigit() and len(n) <= 6 for n in nums):
+        sys.stderr.write(f'SGM_HIP_CENSUS_WINDOW="{raw}" is not <tx>x<ty>[/<step>] | cfg: using 9x7\n')
+        return CENSUS_WINDOW_DEFAULT, False
+    return (int(tx), int(ty), int(step) if "/" in v else 1), False
+
+
 def fill_from_env():
     """SGM_HIP_FILL = off | background | median[:gap[:min]] -> (mode, max_gap, min_neighbours), the
     hole filter of the adapters (the C++ adapter core reads the same variable).
@@ -134,6 +169,8 @@ EXPORTS = [
     "sgm_node_frame", "sgm_node_frame_map_builds",
     "sgm_default_fill_params", "sgm_set_fill_params", "sgm_get_fill_params", "sgm_check_fill_params",
     "sgm_fill_holes", "sgm_debug_fill",
+    "sgm_default_census_window", "sgm_set_census_window", "sgm_get_census_window", "sgm_check_census_window",
+    "sgm_census_window_from_size",
 ]
 
 
@@ -183,6 +220,14 @@ class FillParams(ctypes.Structure):
         for k, v in kw.items():
             setattr(f, k, int(v))
         return f
+
+
+class CensusWindow(ctypes.Structure):
+    """sgm_census_window: taps_x x taps_y comparisons, `step` pixels apart."""
+    _fields_ = [("taps_x", ctypes.c_int), ("taps_y", ctypes.c_int), ("step", ctypes.c_int)]
+
+    def as_tuple(self):
+        return (self.taps_x, self.taps_y, self.step)
 
 
 class CameraInfo(ctypes.Structure):
@@ -329,6 +374,12 @@ def load_library(path=None):
     L.sgm_check_fill_params.argtypes = [P(FillParams)]
     L.sgm_fill_holes.argtypes = [vp, vp, sz, ci, ci, ci, P(FillParams), ci, ci, ci, ci, vp, sz, vp]
     L.sgm_debug_fill.argtypes = [vp, vp, ci, ci, ci, P(FillParams), ci, ci, ci, ci]
+    L.sgm_default_census_window.argtypes = [P(CensusWindow)]
+    L.sgm_default_census_window.restype = None
+    L.sgm_set_census_window.argtypes = [vp, P(CensusWindow)]
+    L.sgm_get_census_window.argtypes = [vp, P(CensusWindow)]
+    L.sgm_check_census_window.argtypes = [P(CensusWindow)]
+    L.sgm_census_window_from_size.argtypes = [ci, P(CensusWindow)]
     _lib = L
     return L
 
@@ -448,6 +499,18 @@ class Engine:
         n = ctypes.c_int()
         self._check(self.lib.sgm_get_census_paths(self.h, ctypes.byref(n)))
         return n.value
+
+    def set_census_window(self, taps_x=9, taps_y=7, step=1):
+        """Census mode: the census window, taps_x x taps_y comparisons `step` pixels apart (taps_x 3,
+        5, 7 or 9, taps_y 3, 5 or 7, step 1 or 2; the default is the 9x7 window). Stored as given;
+        an invalid window fails at match time."""
+        w = CensusWindow(int(taps_x), int(taps_y), int(step))
+        self._check(self.lib.sgm_set_census_window(self.h, ctypes.byref(w)))
+
+    def get_census_window(self):
+        w = CensusWindow()
+        self._check(self.lib.sgm_get_census_window(self.h, ctypes.byref(w)))
+        return w.as_tuple()
 
     def set_raw_format(self, channels=1, gray_set=GRAY_Y14):
         """The frames the match entry points take: 1 channel (8UC1, the default) or 3 (interleaved
@@ -982,6 +1045,8 @@ class MatcherHIPSGM:
         self.census_paths = census_paths_from_env(8) if census_paths is None else int(census_paths)
         self.fill = FillParams(*fill_from_env())
         self.fill_when = fill_when_from_env()
+        # census mode: the census window; with SGM_HIP_CENSUS_WINDOW=cfg setWindowSize drives it
+        self.census_window, self.census_window_cfg = census_window_from_env()
         self.init()
 
     # --- AbstractStereoMatcher ----------------------------------------------------------
@@ -1026,6 +1091,12 @@ class MatcherHIPSGM:
     def setWindowSize(self, window_size):
         self.window_size = window_size
         self.params.block_size = int(window_size)
+        if self.census_window_cfg:
+            self.census_window = census_window_from_size(window_size)
+
+    def setCensusWindow(self, taps_x, taps_y, step=1):
+        """The census mode's window, stored as given (an invalid one fails at match time)."""
+        self.census_window = (int(taps_x), int(taps_y), int(step))
 
     def setInterpolation(self, enable):
         self.interpolate = bool(enable)
@@ -1093,6 +1164,7 @@ class MatcherHIPSGM:
         eng = self._engine_for()
         eng.set_params(params)
         eng.set_census_paths(self.census_paths)
+        eng.set_census_window(*self.census_window)
         eng.set_fill_params(self.effective_fill())
         # colour frames: COLOR_BGR2GRAY on the device, with the grey set of the OpenCV release the
         # compat bits name (COL0_LEGACY marks 3.x: Y14; otherwise 4.x: Y15)
@@ -1297,6 +1369,7 @@ def image_cb(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_mi
             first, second, rl, rr, ml, mr = dr, dl, rect[1], rect[0], mr, ml
         eng.set_params(params)
         eng.set_census_paths(matcher.census_paths)
+        eng.set_census_window(*matcher.census_window)
         eng.set_fill_params(matcher.effective_fill())
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
@@ -1350,6 +1423,7 @@ def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, dep
     try:
         eng.set_params(params)
         eng.set_census_paths(matcher.census_paths)
+        eng.set_census_window(*matcher.census_window)
         eng.set_fill_params(matcher.effective_fill())
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:

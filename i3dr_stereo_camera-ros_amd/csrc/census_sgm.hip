@@ -70,24 +70,8 @@ namespace sgm {
 // 62 bits are produced from the highest down, each compare's result shifted into the code
 // (2 VALU per bit: byte compare, shift-add), instead of a u8 LDS read, compare, 64-bit shift
 // and or per bit. Bit order: LSB-first raster over the window, centre skipped.
+// census_bit: sgm_device.h (shared with census_win.hip).
 // ------------------------------------------------------------------------------------
-// acc = 2 * acc + (byte b of w < c): an SDWA byte compare into vcc and an add-with-carry
-// (b is a constant once the window loops are unrolled)
-#define SGM_CENSUS_BIT(B)                                                              \
-    asm("v_cmp_lt_u32_sdwa vcc, %1, %2 src0_sel:BYTE_" #B " src1_sel:DWORD\n\t"      \
-        "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc"                                       \
-        : "+v"(acc) : "v"(w), "v"(c) : "vcc")
-__device__ __forceinline__ void census_bit(uint32_t& acc, uint32_t w, uint32_t c, int b)
-{
-    switch (b) {
-    case 0: SGM_CENSUS_BIT(0); break;
-    case 1: SGM_CENSUS_BIT(1); break;
-    case 2: SGM_CENSUS_BIT(2); break;
-    default: SGM_CENSUS_BIT(3); break;
-    }
-}
-#undef SGM_CENSUS_BIT
-
 template <int PITCH>
 __device__ __forceinline__ uint64_t census_code_lds(const uint8_t* tile, int ty, int tx)
 {

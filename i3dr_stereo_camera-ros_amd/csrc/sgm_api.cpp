@@ -81,6 +81,47 @@ int sgm_get_census_paths(const sgm_handle* h, int* paths)
     return SGM_OK;
 }
 
+void sgm_default_census_window(sgm_census_window* w)
+{
+    if (w) *w = kCensusWindowDefault;
+}
+
+int sgm_set_census_window(sgm_handle* h, const sgm_census_window* w)
+{
+    if (!h || !w) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->cfg.cwin = *w;                 // checked at match time (prepare), like every parameter
+    return SGM_OK;
+}
+
+int sgm_get_census_window(const sgm_handle* h, sgm_census_window* w)
+{
+    if (!h || !w) return SGM_ERR_ARG;
+    *w = h->cfg.cwin;
+    return SGM_OK;
+}
+
+int sgm_check_census_window(const sgm_census_window* w)
+{
+    if (!w) return SGM_ERR_ARG;
+    std::string err;
+    return census_window_status(*w, err);
+}
+
+// the one table from the node's correlation_window_size slider to a census window
+int sgm_census_window_from_size(int w, sgm_census_window* out)
+{
+    if (!out) return SGM_ERR_ARG;
+    const int s = w | 1;              // even values count as the next odd one
+    if (s <= 3) *out = {3, 3, 1};
+    else if (s == 5) *out = {5, 5, 1};
+    else if (s == 7) *out = {7, 7, 1};
+    else if (s == 9) *out = {9, 7, 1};
+    else if (s <= 13) *out = {7, 7, 2};
+    else *out = {9, 7, 2};
+    return SGM_OK;
+}
+
 void sgm_default_fill_params(sgm_fill_params* p)
 {
     if (p) *p = kFillDefaults;
@@ -333,7 +374,9 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
         return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
     // raw frames: the census mode rectifies inside its tiles, the OCV / BM modes in a pre-pass
     // of each frame (k_rectify_pair) into the handle's grey planes
-    const bool prepass = h->rect_on && h->cfg.params.mode != SGM_MODE_CENSUS8;
+    // (the census mode with a non-default window does the same ahead of its census launch: the
+    // planes are planned with the same flag, and run_batch_census runs the pre-pass itself)
+    const bool prepass = h->rect_on && (h->cfg.params.mode != SGM_MODE_CENSUS8 || census_win_on(h->cfg));
     const bool pipelined = h->cfg.params.mode == SGM_MODE_CENSUS8 && (n >= 2 || h->rect_on) && g.width1 > 0;
     rc = prepare(h, h->cfg, W, H, false, g, l, pipelined ? batch_group(n) : 0, prepass);
     if (rc) return rc;

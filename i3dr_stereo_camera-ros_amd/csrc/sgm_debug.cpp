@@ -72,14 +72,21 @@ int sgm_debug_census(sgm_handle* h, const uint8_t* img, int W, int H, size_t str
 {
     if (!h || !img || !out || W <= 0 || H <= 0 || stride < (size_t)W) return SGM_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    int rc = ensure_stream(h);
-    if (rc || (rc = order_after_last(h, h->stream))) return rc;
+    // the handle's window; an invalid one is an error in the census mode only: the OCV and BM modes
+    // ignore the stored window, so there the call keeps giving the 9x7 codes
+    sgm_census_window cw = h->cfg.cwin;
+    int rc = SGM_OK;
+    if (!census_window_ok(cw)) {
+        if (h->cfg.params.mode == SGM_MODE_CENSUS8) return census_window_status(cw, h->err);
+        cw = kCensusWindowDefault;
+    }
+    if ((rc = ensure_stream(h)) || (rc = order_after_last(h, h->stream))) return rc;
     const size_t WH = (size_t)W * H;
     if ((rc = ensure_ws(h, align_up(WH) + WH * 8))) return rc;
     char* ws = (char*)h->ws.base;
     HIP_TRY(hipMemcpy2DAsync(ws, W, img, stride, W, H, hipMemcpyHostToDevice, h->stream), "H2D");
-    HIP_TRY(sgm::launch_census((const uint8_t*)ws, nullptr, W, W, H, (uint64_t*)(ws + align_up(WH)), nullptr,
-                               h->stream), "census");
+    HIP_TRY(sgm::launch_census_planes(cw, (const uint8_t*)ws, nullptr, W, W, H, (uint64_t*)(ws + align_up(WH)),
+                                      nullptr, h->stream), "census");
     HIP_TRY(hipMemcpyAsync(out, ws + align_up(WH), WH * 8, hipMemcpyDeviceToHost, h->stream), "D2H");
     HIP_TRY(hipStreamSynchronize(h->stream), "sync");
     return SGM_OK;
@@ -105,8 +112,8 @@ int sgm_debug_census_path(sgm_handle* h, const uint8_t* L, const uint8_t* R, int
     uint64_t* cL = (uint64_t*)(ws + l.cL[0]);
     uint64_t* cR = (uint64_t*)(ws + l.cR[0]);
     uint8_t* vols = (uint8_t*)(ws + l.vols[0]);
-    HIP_TRY(sgm::launch_census((const uint8_t*)(ws + l.inL), (const uint8_t*)(ws + l.inR), W, W, H, cL, cR, h->stream),
-            "census");
+    HIP_TRY(sgm::launch_census_planes(c.cwin, (const uint8_t*)(ws + l.inL), (const uint8_t*)(ws + l.inR), W, W, H, cL, cR,
+                                      h->stream), "census");
     const uint32_t* items;
     const int n_items = path_items(h, l, g, 1u << dir, 1, h->stream, &items);
     if (n_items < 0) return n_items;

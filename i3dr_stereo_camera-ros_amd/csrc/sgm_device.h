@@ -394,6 +394,43 @@ struct CensusFrames {
     RectifyIn rect;
 };
 
+// Census windows (sgm_set_census_window). The default is the 9x7 window compiled into
+// census_sgm.hip; every other valid one runs k_census_win (census_win.hip) on 8UC1 planes.
+__host__ __device__ constexpr bool census_window_default(const sgm_census_window& w)
+{
+    return w.taps_x == 9 && w.taps_y == 7 && w.step == 1;
+}
+__host__ __device__ constexpr bool census_window_ok(const sgm_census_window& w)
+{
+    return (w.taps_x == 3 || w.taps_x == 5 || w.taps_x == 7 || w.taps_x == 9) &&
+           (w.taps_y == 3 || w.taps_y == 5 || w.taps_y == 7) && (w.step == 1 || w.step == 2);
+}
+// The images of one k_census_win launch: 8UC1 planes (row stride `stride`) and their code images,
+// left and right of up to kMaxGroup frames. Images >= n are not touched.
+struct WinImages {
+    const uint8_t* src[2 * kMaxGroup];
+    uint64_t* out[2 * kMaxGroup];
+    size_t stride;
+    int n;
+};
+
+// One bit of a census code, acc = 2 * acc + (byte b of w < c): an SDWA byte compare into vcc and
+// an add-with-carry (b is a constant once the window loops are unrolled)
+#define SGM_CENSUS_BIT(B)                                                              \
+    asm("v_cmp_lt_u32_sdwa vcc, %1, %2 src0_sel:BYTE_" #B " src1_sel:DWORD\n\t"      \
+        "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc"                                       \
+        : "+v"(acc) : "v"(w), "v"(c) : "vcc")
+__device__ __forceinline__ void census_bit(uint32_t& acc, uint32_t w, uint32_t c, int b)
+{
+    switch (b) {
+    case 0: SGM_CENSUS_BIT(0); break;
+    case 1: SGM_CENSUS_BIT(1); break;
+    case 2: SGM_CENSUS_BIT(2); break;
+    default: SGM_CENSUS_BIT(3); break;
+    }
+}
+#undef SGM_CENSUS_BIT
+
 // cv::cvtColor(COLOR_BGR2GRAY) of one 8UC3 pixel, bytes in memory order c0, c1, c2
 // (SGM_GRAY_Y14: OpenCV 3.x, 14-bit coefficients; SGM_GRAY_Y15: 4.x, 15-bit; round half up)
 __device__ __forceinline__ int gray_px(int c0, int c1, int c2, int set)

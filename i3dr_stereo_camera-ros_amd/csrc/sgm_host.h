@@ -30,6 +30,7 @@ inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 constexpr sgm_bm_params kBmDefaults = {10, 9};   // texture_threshold, prefilter_size
 constexpr sgm_fill_params kFillDefaults = {SGM_FILL_OFF, 16, 2};   // mode, max_gap, min_neighbours
+constexpr sgm_census_window kCensusWindowDefault = {9, 7, 1};     // taps_x, taps_y, step
 
 // What a handle matches with: the setters write it, every sub-handle family receives it whole.
 struct MatchConfig {
@@ -39,8 +40,17 @@ struct MatchConfig {
     int raw_ch = 1;                   // sgm_set_raw_format: channels of the frames (1, or 3 = 8UC3)
     int gray_set = SGM_GRAY_Y14;      // ... and the COLOR_BGR2GRAY coefficient set used with 3
     sgm_fill_params fill = kFillDefaults;   // sgm_set_fill_params: the hole-filling post filter
+    sgm_census_window cwin = kCensusWindowDefault;   // SGM_MODE_CENSUS8 only (sgm_set_census_window)
 };
 inline bool fill_on(const MatchConfig& c) { return c.fill.mode != SGM_FILL_OFF; }
+// the census runs as its own launch on 8UC1 planes (census_win.hip): the census mode with a
+// window other than the default
+inline bool census_win_on(const MatchConfig& c)
+{
+    return c.params.mode == SGM_MODE_CENSUS8 && !census_window_default(c.cwin);
+}
+// ... and its frames are colour and / or raw, so a pre-pass fills the grey planes first
+inline bool census_win_prepass(const MatchConfig& c, bool rect_on) { return census_win_on(c) && (rect_on || c.raw_ch == 3); }
 
 struct Workspace {
     void* base = nullptr;
@@ -155,6 +165,7 @@ struct Layout {
     size_t ores = 0;                                       // ocv: per-pixel results of k_ocv_vwta
     size_t bmL = 0, bmR = 0, bmV = 0;                      // bm: pre-filtered images, HBM column sums
     size_t grayL = 0, grayR = 0;                           // ocv / bm with colour or raw frames: the grey planes
+                                                           // (census with a non-default window: a pair per group frame)
     sgm::BmPlan bm{};                                      // bm: tiling of the fused kernel
     size_t tmp = 0, lab = 0, cnt = 0;                      // post
     size_t inL = 0, inR = 0, out = 0, outf = 0;            // host-API staging (int16 / float out)
@@ -242,6 +253,7 @@ int speckle_scale(int mode);
 Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group = 0, int n_cu = 0, bool rect = false);
 Layout make_post_layout(const sgm_params& p, const Geom& g, bool fill = false);
 int fill_params_status(const sgm_fill_params& f, std::string& err);
+int census_window_status(const sgm_census_window& w, std::string& err);
 int batch_group(int n);
 bool ocv_vwta_on(const Geom& g, int fullDP);
 int ocv_batch_lanes(int n);

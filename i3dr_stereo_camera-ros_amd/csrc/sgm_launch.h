@@ -24,6 +24,11 @@ hipError_t launch_census_fused(const PathFrames& pf, const WtaFrames& wf, const 
                                hipStream_t st);
 hipError_t launch_census_rowfin(const WtaFrames& wf, const Geom& g, size_t out_stride, hipStream_t st);
 
+// census_win.hip
+hipError_t launch_census_win(const WinImages& wi, int W, int H, const sgm_census_window& cw, hipStream_t st);
+hipError_t launch_census_planes(const sgm_census_window& cw, const uint8_t* L, const uint8_t* R, size_t stride, int W,
+                                int H, uint64_t* cL, uint64_t* cR, hipStream_t st);
+
 // rectify.hip
 hipError_t launch_rectify_map(const double* K, const double* dist, const double* ir, int W, int H, float* mx,
                               float* my, size_t stride, hipStream_t st);

@@ -75,7 +75,9 @@ int node_frame(sgm_handle* h, const sgm_camera_info& cl, const sgm_camera_info& 
     if (g.width1 <= 0) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
     const sgm_params& p = h->cfg.params;
     const bool census = p.mode == SGM_MODE_CENSUS8;
-    if ((rc = prepare(h, h->cfg, W, H, false, g, l, census ? batch_group(1) : 0, !census))) return rc;
+    // the pre-pass into the grey planes: the OCV / BM modes, and the census with a non-default window
+    if ((rc = prepare(h, h->cfg, W, H, false, g, l, census ? batch_group(1) : 0, !census || census_win_on(h->cfg))))
+        return rc;
     if ((rc = ensure_cubic_table(h))) return rc;
     hipStream_t st = h->stream;
     if (!h->cpy) HIP_TRY(hipStreamCreateWithFlags(&h->cpy, hipStreamNonBlocking), "hipStreamCreate");

@@ -201,6 +201,16 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
     StageRec rec{h};
     if (h->profiling) h->prof_frames++;
     const int ch = h->cfg.raw_ch == 3 ? 3 : 1;
+    // census with a non-default window: its own launch on 8UC1 planes (colour frames converted
+    // into the grey planes first, like the OCV modes'). Both images are needed at once, so the
+    // right image's copy is issued and waited for up front.
+    const bool win = census_win_on(h->cfg) && g.width1 > 0;
+    const bool split_r = copy_r && !win;
+    if (copy_r && win) {
+        const hipEvent_t r_ready = copy_r();
+        if (!r_ready) return SGM_ERR_DEVICE;
+        HIP_TRY(hipStreamWaitEvent(st, r_ready, 0), "hipStreamWaitEvent");
+    }
     if (raw && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
         // raw frames (the node's imageCb): both images through the handle's maps into the grey
         // planes, colour converted after the remap, then the unchanged pipeline on those. Bytes:
@@ -213,9 +223,10 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
                                          raw->R, raw->stride, st), "rectify");
         if (rect_ev) HIP_TRY(hipEventRecord(rect_ev, st), "hipEventRecord");   // the rectified images are written
         dL = GL; dR = GR; stride = g.W;
-    } else if (ch == 3 && p.mode != SGM_MODE_CENSUS8 && g.width1 > 0) {
+    } else if (ch == 3 && (p.mode != SGM_MODE_CENSUS8 || win) && g.width1 > 0) {
         // colour frames: COLOR_BGR2GRAY of both images into the handle's grey planes, then the
-        // unchanged pipeline on those (the census mode converts inside its tiles instead)
+        // unchanged pipeline on those (the census mode with its default window converts inside
+        // its tiles instead)
         uint8_t* GL = (uint8_t*)(ws + l.grayL);
         uint8_t* GR = (uint8_t*)(ws + l.grayR);
         rec.begin("gray", 6 * WH + 2 * WH);
@@ -238,8 +249,10 @@ int run_pipeline(sgm_handle* h, const Layout& l, const Geom& g, const uint8_t* d
         uint64_t* cL = (uint64_t*)(ws + l.cL[0]);
         uint64_t* cR = (uint64_t*)(ws + l.cR[0]);
         uint8_t* vols = (uint8_t*)(ws + l.vols[0]);
-        rec.begin("census", 2 * ch * WH + 16 * WH);
-        if (copy_r) {
+        rec.begin(win ? "census_win" : "census", (win ? 2 : 2 * ch) * WH + 16 * WH);
+        if (win) {    // dL / dR are 8UC1 here (colour frames went through the grey planes above)
+            HIP_TRY(sgm::launch_census_planes(h->cfg.cwin, dL, dR, stride, g.W, g.H, cL, cR, st), "census_win");
+        } else if (split_r) {
             HIP_TRY(sgm::launch_census(dL, nullptr, stride, g.W, g.H, cL, nullptr, st, ch, h->cfg.gray_set), "census L");
             const hipEvent_t r_ready = copy_r();
             if (!r_ready) return SGM_ERR_DEVICE;
@@ -401,9 +414,49 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
     auto hk_in = [&](int k) { return hooks ? hooks->inputs(k * G, frames_of(k)) : 0; };
     auto hk_free = [&](int k) { return hooks ? hooks->outputs_free(k * G, frames_of(k)) : 0; };
     auto hk_done = [&](int k) { return hooks ? hooks->outputs_done(k * G, frames_of(k)) : 0; };
+    // A non-default window (sgm_set_census_window): the census of group k is a launch of its own
+    // on the stream (stage census_win, all images of the group at once) and the fused launches get
+    // an empty CensusFrames. Colour and / or raw frames first go through the OCV modes' pre-pass,
+    // frame by frame into the group's grey planes (stage rectify, which also writes the requested
+    // rectified images, or gray).
+    const bool win = census_win_on(h->cfg);
+    const bool pre = census_win_prepass(h->cfg, h->rect_on);
+    auto census_win_group = [&](int k) -> int {
+        sgm::WinImages wi{};
+        wi.n = 2 * frames_of(k);
+        wi.stride = pre ? (size_t)g.W : stride;
+        for (int f = 0; f < frames_of(k); f++) {
+            const int i = k * G + f;
+            const uint8_t* pl = dLs[i];
+            const uint8_t* pr = dRs[i];
+            if (pre) {
+                uint8_t* GL = (uint8_t*)(ws + l.grayL) + (size_t)f * g.W * g.H;
+                uint8_t* GR = (uint8_t*)(ws + l.grayR) + (size_t)f * g.W * g.H;
+                if (h->rect_on) {
+                    uint8_t* rl = rectLs ? rectLs[i] : nullptr;
+                    uint8_t* rr = rectRs ? rectRs[i] : nullptr;
+                    rec.begin("rectify", (16 + 2 * ch + 2 + ch * ((rl ? 1 : 0) + (rr ? 1 : 0))) * WH);
+                    HIP_TRY(sgm::launch_rectify_pair(h->rect, pl, pr, stride, ch, h->cfg.gray_set, g.W, g.H, GL, GR, rl, rr,
+                                                     rect_stride, st), "rectify");
+                    if (node && node->rect_ev) HIP_TRY(hipEventRecord(node->rect_ev, st), "hipEventRecord");
+                } else {
+                    rec.begin("gray", 6 * WH + 2 * WH);
+                    HIP_TRY(sgm::launch_bgr2gray(pl, pr, stride, g.W, g.H, GL, GR, g.W, h->cfg.gray_set, st), "gray");
+                }
+                pl = GL; pr = GR;
+            }
+            wi.src[2 * f] = pl; wi.out[2 * f] = (uint64_t*)(ws + l.cL[code_set(k, f)]);
+            wi.src[2 * f + 1] = pr; wi.out[2 * f + 1] = (uint64_t*)(ws + l.cR[code_set(k, f)]);
+        }
+        rec.begin("census_win", (2 + 16) * WH * frames_of(k));
+        HIP_TRY(sgm::launch_census_win(wi, g.W, g.H, h->cfg.cwin, st), "census_win");
+        return SGM_OK;
+    };
     int hrc = hk_in(0);
     if (hrc) return hrc;
-    if (h->rect_on) {           // remap + census of the first group, one launch
+    if (win) {
+        if ((hrc = census_win_group(0))) return hrc;
+    } else if (h->rect_on) {    // remap + census of the first group, one launch
         rec.begin("rectify+census", (census_bytes + 16 * WH) * frames_of(0));
         HIP_TRY(sgm::launch_census_tiles(census_frames(0), g.W, g.H, st), "rectify+census");
         if (node && node->rect_ev) HIP_TRY(hipEventRecord(node->rect_ev, st), "hipEventRecord");
@@ -419,6 +472,8 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
         // disparities of group k - 1 (WTA, or up+WTA and the row finish after it)
         if (k + 1 < ng && ng > 1 && (hrc = hk_in(k + 1))) return hrc;
         if (k > 0 && (hrc = hk_free(k - 1))) return hrc;
+        // a non-default window: the next group's census ahead of this launch instead of in its tail
+        if (win && k + 1 < ng && (hrc = census_win_group(k + 1))) return hrc;
         if (up && k < ng) {
             // the last group sweeps all eight directions (its WTA rows follow alone: a lone
             // launch of up+WTA blocks would be one long latency-bound chain per column block)
@@ -426,7 +481,7 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
             sgm::PathFrames pf = path_frames(k);
             pf.skip_dirs = last ? 0u : 2u;
             const sgm::WtaFrames wf = k > 0 ? wta_frames(k - 1) : sgm::WtaFrames{};
-            const sgm::CensusFrames cf = k + 1 < ng ? census_frames(k + 1) : sgm::CensusFrames{};
+            const sgm::CensusFrames cf = k + 1 < ng && !win ? census_frames(k + 1) : sgm::CensusFrames{};
             // stage name and algorithmic bytes (the canonical dataflow: the dir-1 volume of an
             // up+WTA frame counted as written and read, as if it existed) from the launch's parts
             const char* name8 = last ? (wf.n ? "paths8+up_wta" : "paths8")
@@ -454,9 +509,9 @@ int run_batch_census(sgm_handle* h, const Layout& l, const Geom& g, const uint8_
             HIP_TRY(sgm::launch_census_paths(path_frames(0), l.vol_bytes, g, items, n_items, st), "paths");
         } else {
             const sgm::WtaFrames wf = k > 0 ? wta_frames(k - 1) : sgm::WtaFrames{};
-            const sgm::CensusFrames cf = k + 1 < ng ? census_frames(k + 1) : sgm::CensusFrames{};
-            const char* name8 = wf.n ? (cf.n ? "paths8+wta_lr+census" : "paths8+wta_lr") : "paths8+census";
-            const char* name4 = wf.n ? (cf.n ? "paths4+wta_lr+census" : "paths4+wta_lr") : "paths4+census";
+            const sgm::CensusFrames cf = k + 1 < ng && !win ? census_frames(k + 1) : sgm::CensusFrames{};
+            const char* name8 = wf.n ? (cf.n ? "paths8+wta_lr+census" : "paths8+wta_lr") : (cf.n ? "paths8+census" : "paths8");
+            const char* name4 = wf.n ? (cf.n ? "paths4+wta_lr+census" : "paths4+wta_lr") : (cf.n ? "paths4+census" : "paths4");
             rec.begin(np == 4 ? name4 : name8,
                       np * cells * frames_of(k) + (np * cells + 2 * WH) * wf.n + census_bytes * cf.n);
             HIP_TRY(sgm::launch_census_fused(path_frames(k), wf, cf, l.vol_bytes, g, items, n_items, dst_stride, false,
@@ -514,6 +569,7 @@ int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geo
     if (c.params.mode == SGM_MODE_CENSUS8 && c.census_paths != 4 && c.census_paths != 8)
         return fail(h, SGM_ERR_PARAM, "census paths must be 4 or 8 (sgm_set_census_paths), got " +
                                           std::to_string(c.census_paths));
+    if (c.params.mode == SGM_MODE_CENSUS8 && (rc = census_window_status(c.cwin, h->err))) return rc;
     if ((rc = raw_format_status(h, c))) return rc;
     if ((rc = fill_params_status(c.fill, h->err))) return rc;
     if ((rc = ensure_stream(h))) return rc;

@@ -143,8 +143,8 @@ static bool use_up_wta()
     return !e || std::atoi(e) != 0;
 }
 
-// rect: the frames are raw (sgm_set_rectification) and the mode is OCV or BM, whose pre-pass
-// rectifies them into the grey planes.
+// rect: the frames are raw (sgm_set_rectification) and a pre-pass rectifies them into the grey
+// planes: the OCV and BM modes, and the census mode with a non-default window.
 Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group, int n_cu, bool rect)
 {
     const sgm_params& p = c.params;
@@ -204,6 +204,8 @@ Layout make_layout(const MatchConfig& c, const Geom& g, bool host_io, int group,
     l.tmp = take(WH * 2 * (size_t)std::max(group, 1));   // raw disparity before the median (per frame of a group)
     if (p.speckle_window_size > 0) { l.lab = take(WH * 4); l.cnt = take(WH * 4); }
     if ((ch == 3 || rect) && p.mode != SGM_MODE_CENSUS8) { l.grayL = take(WH); l.grayR = take(WH); }
+    // census with a non-default window: k_census_win reads one grey plane pair per frame of a group
+    if (census_win_prepass(c, rect)) { l.grayL = take(WH * l.group); l.grayR = take(WH * l.group); }
     if (host_io) { l.inL = take(WH * ch); l.inR = take(WH * ch); l.out = take(WH * 2); l.outf = take(WH * 4); }
     if (fill_on(c)) {
         l.fill = true;
@@ -251,6 +253,15 @@ int fill_params_status(const sgm_fill_params& f, std::string& err)
         return SGM_ERR_PARAM;
     }
     return SGM_OK;
+}
+
+// sgm_set_census_window stores anything; a census match needs one of the 24 windows
+int census_window_status(const sgm_census_window& w, std::string& err)
+{
+    if (census_window_ok(w)) return SGM_OK;
+    err = "census window: taps_x must be 3, 5, 7 or 9, taps_y 3, 5 or 7 and step 1 or 2 (sgm_set_census_window), got " +
+          std::to_string(w.taps_x) + "x" + std::to_string(w.taps_y) + "/" + std::to_string(w.step);
+    return SGM_ERR_PARAM;
 }
 
 // OpenCV modes: the vertical direction of the last group fused with the WTA (k_ocv_vwta)

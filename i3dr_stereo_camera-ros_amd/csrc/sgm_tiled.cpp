@@ -164,7 +164,8 @@ extern "C" int sgm_match_tiled_device(sgm_handle* h, const uint8_t* dL, const ui
 
 // ------------------------------------------------------------------ exact tile mode ----
 // SURVEY §8(e) "single huge frame", exact mode. Band b (rows [c0, c1)) runs on its own
-// handle: census of its rows (+3 image rows of halo, so the codes equal the full frame's),
+// handle: census of its rows (+3 * step image rows of halo, the reach of the census window, so the
+// codes equal the full frame's),
 // horizontal scans (band-local), then its downward sweeps continue the lines of band b-1
 // from band b-1's last volume row and its upward sweeps those of band b+1 from its first
 // row. The boundary rows (3 directions x width1 x D u8 per seam and sweep) move between
@@ -253,6 +254,9 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
     // the seam exchange carries three directions per sweep family (bnd_slot_of): 8 paths only
     if (h->cfg.census_paths != 8)
         return fail(h, SGM_ERR_UNSUPPORTED, "the exact tile mode runs with 8 census paths (sgm_set_census_paths)");
+    if ((rc = census_window_status(h->cfg.cwin, h->err))) return rc;
+    const sgm_census_window cw = h->cfg.cwin;
+    const int ih = 3 * cw.step;       // image rows a band's census needs beyond its own: the window's reach
     const int nb = n_bands;
     while ((int)h->bands.size() < nb) h->bands.push_back(nullptr);
     std::vector<int> c(nb + 1);
@@ -266,7 +270,7 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
         if (!bh && (rc = sgm_create(&bh, dev))) return fail(h, rc, "cannot open device " + std::to_string(dev));
         bh->cfg = h->cfg;
         if ((rc = make_geom(p, W, c[b + 1] - c[b], g[b], h->err))) return rc;
-        const int e0 = std::max(0, c[b] - 3), e1 = std::min(H, c[b + 1] + 3);
+        const int e0 = std::max(0, c[b] - ih), e1 = std::min(H, c[b + 1] + ih);
         bl[b] = make_band_layout(g[b], e1 - e0);
         if ((rc = band_prepare(bh, g[b], bl[b]))) return fail(h, rc, "band " + std::to_string(b) + ": " + bh->err);
         if ((rc = ensure_pin(bh, 2 * (size_t)W * (e1 - e0)))) return fail(h, rc, bh->err);
@@ -334,7 +338,7 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
     for (int b = 0; b < nb; b++) {
         sgm_handle* bh = h->bands[b];
         BAND_TRY(b, hipSetDevice(bh->device), "hipSetDevice");
-        const int e0 = std::max(0, c[b] - 3), e1 = std::min(H, c[b + 1] + 3), He = e1 - e0;
+        const int e0 = std::max(0, c[b] - ih), e1 = std::min(H, c[b + 1] + ih), He = e1 - e0;
         const size_t n = (size_t)W * He;
         for (int y = 0; y < He; y++) {
             std::memcpy(bh->pin + (size_t)y * W, L + (size_t)(e0 + y) * stride, W);
@@ -345,14 +349,15 @@ int run_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
         BAND_TRY(b, hipMemcpyAsync(ws(b, bl[b].inR), bh->pin + n, n, hipMemcpyHostToDevice, bh->stream), "H2D");
         tt_end(b, "h2d", bh->stream);
         tt_begin(b, bh->stream);
-        BAND_TRY(b, sgm::launch_census((const uint8_t*)ws(b, bl[b].inL), (const uint8_t*)ws(b, bl[b].inR), W, W, He,
-                                       (uint64_t*)ws(b, bl[b].cL), (uint64_t*)ws(b, bl[b].cR), bh->stream), "census");
+        BAND_TRY(b, sgm::launch_census_planes(cw, (const uint8_t*)ws(b, bl[b].inL), (const uint8_t*)ws(b, bl[b].inR), W, W,
+                                              He, (uint64_t*)ws(b, bl[b].cL), (uint64_t*)ws(b, bl[b].cR), bh->stream),
+                 "census");
         tt_end(b, "census", bh->stream);
         BAND_TRY(b, hipEventRecord(bh->bev[EV_CENSUS], bh->stream), "event");
     }
     auto frames = [&](int b) {
         sgm::PathFrames pf{};
-        const size_t skip = (size_t)(c[b] - std::max(0, c[b] - 3)) * W;   // codes of the band's first row
+        const size_t skip = (size_t)(c[b] - std::max(0, c[b] - ih)) * W;  // codes of the band's first row
         pf.cL[0] = (const uint64_t*)ws(b, bl[b].cL) + skip;
         pf.cR[0] = (const uint64_t*)ws(b, bl[b].cR) + skip;
         pf.vols[0] = (uint8_t*)ws(b, bl[b].vols);

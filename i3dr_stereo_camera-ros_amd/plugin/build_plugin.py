@@ -1,6 +1,6 @@
 """Build the OpenCV-free plugin core (hip_sgm_core.cpp) into lib/libsgm_plugin_core.so and
 its C++ test drivers lib/plugin_core_test, lib/plugin_bm_test, lib/plugin_paths_test,
-lib/plugin_frame_test and lib/plugin_fill_test, all linked against lib/libsgm_hip.so with g++.
+lib/plugin_frame_test, lib/plugin_fill_test and lib/plugin_window_test, all linked against lib/libsgm_hip.so with g++.
 (matcherHIPSGM.cpp needs OpenCV + the reference headers and is built inside the ROS tree.)"""
 import os
 import subprocess
@@ -50,6 +50,11 @@ def build():
     if _stale(fill_drv, deps + [fill_src]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
                               [fill_src, core_src, "-o", fill_drv] + link)
+    window_src = os.path.join(HERE, "plugin_window_test.cpp")
+    window_drv = os.path.join(LIBDIR, "plugin_window_test")
+    if _stale(window_drv, deps + [window_src]):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
+                              [window_src, core_src, "-o", window_drv] + link)
     return so
 
 

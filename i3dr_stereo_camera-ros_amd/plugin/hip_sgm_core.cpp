@@ -73,6 +73,48 @@ static std::string trimmed_lower(const char* e)
     return v;
 }
 
+// SGM_HIP_CENSUS_WINDOW = <tx>x<ty>[/<step>] | cfg: the census mode's window
+// (sgm_set_census_window). Case and surrounding blanks are ignored. "7x7" or "9x7/2": that window,
+// each number 1 to 6 decimal digits, passed on as it is (one that is not among the 24 valid windows
+// fails at match time); the text splits at the first '/' and then at the first 'x'. "cfg":
+// *follow_cfg, setWindowSize drives the window. Unset or blank: the 9x7 default. An unparsable
+// value gives the default and a note on stderr (the Python mirror's census_window_from_env does the
+// same).
+sgm_census_window census_window_from_env(bool* follow_cfg)
+{
+    sgm_census_window def;
+    sgm_default_census_window(&def);
+    if (follow_cfg) *follow_cfg = false;
+    const char* e = std::getenv("SGM_HIP_CENSUS_WINDOW");
+    if (!e) return def;
+    const std::string v = trimmed_lower(e);
+    if (v.empty()) return def;
+    if (v == "cfg") {
+        if (follow_cfg) *follow_cfg = true;
+        return def;
+    }
+    const size_t slash = v.find('/');
+    const std::string size = v.substr(0, slash);
+    const size_t x = size.find('x');
+    bool ok = x != std::string::npos;
+    std::vector<std::string> nums;
+    if (ok) {
+        nums.push_back(size.substr(0, x));
+        nums.push_back(size.substr(x + 1));
+        if (slash != std::string::npos) nums.push_back(v.substr(slash + 1));
+    }
+    for (const std::string& n : nums) {
+        ok = ok && !n.empty() && n.size() <= 6;
+        for (char c : n) ok = ok && c >= '0' && c <= '9';
+    }
+    if (!ok) {
+        std::cerr << "SGM_HIP_CENSUS_WINDOW=\"" << e << "\" is not <tx>x<ty>[/<step>] | cfg: using 9x7" << std::endl;
+        return def;
+    }
+    return sgm_census_window{std::atoi(nums[0].c_str()), std::atoi(nums[1].c_str()),
+                             nums.size() > 2 ? std::atoi(nums[2].c_str()) : 1};
+}
+
 // SGM_HIP_FILL = off | background | median[:gap[:min]]: the hole filter of the adapter
 // (sgm_set_fill_params). Case and surrounding blanks are ignored; gap and min are 1 to 6 decimal
 // digits (defaults 16 and 2) and are passed on as they are (a value out of range fails at match
@@ -125,6 +167,7 @@ bool fill_when_interp_from_env()
 MatcherCore::MatcherCore(int device, int mode) : device_(device)
 {
     census_paths_ = census_paths_from_env(8);
+    census_window_ = census_window_from_env(&census_window_cfg_);
     fill_ = fill_from_env();
     fill_when_interp_ = fill_when_interp_from_env();
     if (mode < 0) {
@@ -180,7 +223,11 @@ void MatcherCore::setDisparityRange(int r, int image_width)
     r = r > 0 ? r : ((image_width / 8) + 15) & -16;
     params_.num_disparities = r;
 }
-void MatcherCore::setWindowSize(int w) { params_.block_size = w; }
+void MatcherCore::setWindowSize(int w)
+{
+    params_.block_size = w;
+    if (census_window_cfg_) (void)sgm_census_window_from_size(w, &census_window_);   // the one slider table
+}
 void MatcherCore::setMinDisparity(int d) { params_.min_disparity = d; }
 void MatcherCore::setUniquenessRatio(int r) { params_.uniqueness_ratio = r; }
 void MatcherCore::setSpeckleFilterWindow(int w) { params_.speckle_window_size = w; }
@@ -193,6 +240,8 @@ void MatcherCore::setInterpolation(bool e) { interpolate_ = e; }
 void MatcherCore::setMode(int m) { params_.mode = m; }
 void MatcherCore::setOcvCompat(int bits) { params_.ocv_compat = bits; }
 void MatcherCore::setCensusPaths(int paths) { census_paths_ = paths; }
+void MatcherCore::setCensusWindow(int taps_x, int taps_y, int step) { census_window_ = sgm_census_window{taps_x, taps_y, step}; }
+void MatcherCore::setCensusWindowFollowsSize(bool follow) { census_window_cfg_ = follow; }
 void MatcherCore::setHoleFilling(int mode, int max_gap, int min_neighbours) { fill_ = sgm_fill_params{mode, max_gap, min_neighbours}; }
 void MatcherCore::setFillWhenInterp(bool interp) { fill_when_interp_ = interp; }
 sgm_fill_params MatcherCore::effectiveFill() const
@@ -237,6 +286,7 @@ int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
     if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
     if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
+    if (rc == SGM_OK) rc = sgm_set_census_window(handle_, &census_window_);
     const sgm_fill_params fill = effectiveFill();
     if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
     if (rc == SGM_OK && keep_reg_ && outf) {
@@ -302,6 +352,7 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
     if (rc == SGM_OK) rc = sgm_set_params(handle_, &p);
     if (rc == SGM_OK) rc = sgm_set_bm_params(handle_, &bm);
     if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
+    if (rc == SGM_OK) rc = sgm_set_census_window(handle_, &census_window_);
     if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
     // colour frames: the grey set of the OpenCV release the compat bits name (COL0_LEGACY marks 3.x)
     if (rc == SGM_OK)

@@ -20,6 +20,10 @@ namespace sgm_hip {
 int ocv_compat_from_env(int fallback);
 // SGM_HIP_CENSUS_PATHS (4 | 8, any integer is passed on), else `fallback`
 int census_paths_from_env(int fallback);
+// SGM_HIP_CENSUS_WINDOW (<tx>x<ty>[/<step>] | cfg; each number 1 to 6 digits, passed on as it is).
+// Returns the window; *follow_cfg: setWindowSize drives it (cfg). Unset, blank or unparsable (with
+// a note on stderr): the 9x7 default and no following.
+sgm_census_window census_window_from_env(bool* follow_cfg);
 // SGM_HIP_FILL (off | background | median[:gap[:min]]; gap and min: 1 to 6 digits, defaults 16 and
 // 2, passed on as they are); unset, blank or unparsable (with a note on stderr): off
 sgm_fill_params fill_from_env();
@@ -53,6 +57,14 @@ public:
     // SGM_MODE_CENSUS8 only: 8 or 4 aggregation paths (sgm_set_census_paths; default: the
     // SGM_HIP_CENSUS_PATHS env var, else 8). Forward and backward matches both use it.
     void setCensusPaths(int paths);
+    // SGM_MODE_CENSUS8 only: the census window (sgm_set_census_window; default: the
+    // SGM_HIP_CENSUS_WINDOW env var, else 9x7 step 1). Stored as given: an invalid window fails at
+    // match time. With SGM_HIP_CENSUS_WINDOW=cfg (or setCensusWindowFollowsSize(true)) setWindowSize
+    // also sets it, through sgm_census_window_from_size; otherwise setWindowSize leaves it alone (the
+    // node's default slider value is 15 and existing census users keep their results). Forward and
+    // backward matches and imageCb all use it.
+    void setCensusWindow(int taps_x, int taps_y, int step = 1);
+    void setCensusWindowFollowsSize(bool follow);
     // The hole filter after every match (sgm_set_fill_params; default: the SGM_HIP_FILL env var,
     // else off). Stored as given: bad values fail at match time. With SGM_HIP_FILL_WHEN=interp the
     // interp flag drives it instead: setInterpolation(true) returns the forward disparity filled
@@ -111,6 +123,8 @@ public:
     bool interpolation() const { return interpolate_; }
     int disparityRange() const { return params_.num_disparities; }
     int censusPaths() const { return census_paths_; }
+    const sgm_census_window& censusWindow() const { return census_window_; }
+    bool censusWindowFollowsSize() const { return census_window_cfg_; }
     const sgm_fill_params& holeFilling() const { return fill_; }
     const std::string& lastError() const { return err_; }
     // SGBM modes: cv::ximgproc::createRightMatcher of a StereoSGBM. BM mode: of a StereoBM —
@@ -128,6 +142,8 @@ private:
     sgm_params params_{};
     sgm_bm_params bm_{};
     int census_paths_ = 8;
+    sgm_census_window census_window_{9, 7, 1};
+    bool census_window_cfg_ = false;   // setWindowSize drives census_window_
     sgm_fill_params fill_{};
     bool fill_when_interp_ = false;
     bool interpolate_ = false;

@@ -108,6 +108,8 @@ void MatcherHIPSGM::setHoleFilling(int mode, int max_gap, int min_neighbours)
   core_.setHoleFilling(mode, max_gap, min_neighbours);
 }
 
+void MatcherHIPSGM::setCensusWindow(int taps_x, int taps_y, int step) { core_.setCensusWindow(taps_x, taps_y, step); }
+
 void MatcherHIPSGM::setInterpolation(bool enable)
 {
   this->interpolate = enable;

@@ -11,7 +11,8 @@ class MatcherHIPSGM : public AbstractStereoMatcher
 {
 public:
   // mode: an SGM_MODE_* of sgm_hip.h; -1 reads SGM_HIP_MODE (default SGM_MODE_OCV_SGBM5).
-  // The census mode's path set (8 or 4) comes from SGM_HIP_CENSUS_PATHS (hip_sgm_core.h setCensusPaths).
+  // The census mode's path set (8 or 4) comes from SGM_HIP_CENSUS_PATHS (hip_sgm_core.h setCensusPaths),
+  // its census window from SGM_HIP_CENSUS_WINDOW (setCensusWindow below).
   // SGM_MODE_OCV_BM (3) makes this the drop-in for MatcherOpenCVBlock (cv::StereoBM).
   explicit MatcherHIPSGM(std::string &param_file, cv::Size _image_size, int mode = -1)
       : AbstractStereoMatcher(param_file, _image_size), core_(0, mode)
@@ -46,6 +47,10 @@ public:
   // SGM_HIP_FILL_WHEN=interp, setInterpolation drives it in place of the Q3 right-view result
   // (hip_sgm_core.h setHoleFilling).
   void setHoleFilling(int mode, int max_gap = 16, int min_neighbours = 2);
+  // The census mode's window (default: env SGM_HIP_CENSUS_WINDOW, else 9x7 step 1). With
+  // SGM_HIP_CENSUS_WINDOW=cfg, setWindowSize (the node's correlation_window_size slider) drives it
+  // through sgm_census_window_from_size (hip_sgm_core.h setCensusWindow).
+  void setCensusWindow(int taps_x, int taps_y, int step = 1);
 
   // cv::StereoBM parameters: used in BM mode, ignored by the SGM modes (matcherOpenCVSGBM.h:31-34)
   void setTextureThreshold(int threshold);

@@ -41,7 +41,8 @@ extern "C" {
  * existing struct or signature (sgm_params stays 15 ints), so the version did not move; a
  * caller that needs them checks for the symbols. The colour entry points (sgm_bgr2gray,
  * sgm_remap_cubic_c3, sgm_set_raw_format, sgm_get_raw_format) came the same way, and so did
- * sgm_node_frame / sgm_node_frame_map_builds with their two structs.                       */
+ * sgm_node_frame / sgm_node_frame_map_builds with their two structs, and the census window
+ * entry points (sgm_*_census_window*) with sgm_census_window.                               */
 #define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
@@ -96,7 +97,7 @@ typedef struct sgm_params {
     int mode;                 /* SGM_MODE_*                                               */
     int min_disparity;        /* setMinDisparity                  (cfg min_disparity)     */
     int num_disparities;      /* setDisparityRange, multiple of 16 (cfg disparity_range)  */
-    int block_size;           /* setWindowSize: OCV SAD window (cfg correlation_window_size); census: ignored */
+    int block_size;           /* setWindowSize: OCV SAD window (cfg correlation_window_size); census: ignored (its window: sgm_set_census_window) */
     int p1;                   /* setP1 (float in the reference API, truncated like OpenCV's int setter) */
     int p2;                   /* setP2                                                    */
     int uniqueness_ratio;     /* setUniquenessRatio (percent)                             */
@@ -172,6 +173,45 @@ int  sgm_get_bm_params(const sgm_handle* h, sgm_bm_params* p);
  * sgm_stage_bytes follows the set (paths4: 4 bytes per cell).                               */
 int  sgm_set_census_paths(sgm_handle* h, int paths);
 int  sgm_get_census_paths(const sgm_handle* h, int* paths);
+
+/* Census mode: the census window, per handle: what setWindowSize means for the census matcher
+ * (the I3DR matcher resizes its census window the same way). Specified by this project;
+ * tests/census_window_reference.py is the executable statement. A window is
+ * (taps_x, taps_y, step) with taps_x in {3, 5, 7, 9}, taps_y in {3, 5, 7}, step in {1, 2}; the
+ * default {9, 7, 1} is the 9x7 window.
+ *   - tap (j, i), j in [-(taps_y-1)/2, (taps_y-1)/2], i in [-(taps_x-1)/2, (taps_x-1)/2], compares
+ *     I(clamp(y + step*j), clamp(x + step*i)) < I(y, x) (replicate clamping, as the 9x7 census);
+ *   - its bit is the one the offset (dy = j, dx = i) has in the 9x7 code: raster order over
+ *     dy = -3..3, dx = -4..4, centre skipped, LSB first; bits of taps outside the window are 0.
+ * So a code stays a uint64_t of at most 62 bits and the Hamming cost stays <= 62; a dense
+ * (step 1) window's code equals code_9x7 & mask(taps_x, taps_y); {9, 7, 2} spans 17 x 13 pixels;
+ * and everything after the codes (path recurrence with its P2 <= 193 clamp, WTA, uniqueness,
+ * sub-pixel, LR check, median, speckles, hole filling, 4 or 8 paths) is unchanged.
+ * Like every setter sgm_set_census_window stores any value: an invalid window is SGM_ERR_PARAM
+ * at match time in the census mode; the OCV and BM modes ignore it. Honoured by sgm_match,
+ * sgm_match_f32, sgm_match_device, sgm_match_device_batch[_rect], sgm_match_batch,
+ * sgm_node_frame, sgm_match_tiled, sgm_match_tiled_device and sgm_match_tiled_exact (whose band
+ * images carry 3 * step halo rows), with colour and raw frames wherever the default window takes
+ * them; sub-handles inherit it; sgm_debug_census and sgm_debug_census_path use it too.
+ * With the default window nothing changes (same launches, stage names and workspace). With any
+ * other the census is a launch of its own on 8UC1 planes (profiling stage `census_win`,
+ * sgm_stage_bytes 1 B/px read and 8 B/px written per image) and the pipelined batch's fused
+ * launches carry no census (their stage names lose the `+census`); colour and / or raw frames
+ * first go through the pre-pass of the OCV modes into per-handle grey planes (stage `gray`, or
+ * `rectify`, which also writes the requested rectified images: bit-identical to the default
+ * window's). Added under ABI version 5 (no existing struct or signature changed): callers check
+ * for the symbols.                                                                             */
+typedef struct sgm_census_window { int taps_x, taps_y, step; } sgm_census_window;
+/* {9, 7, 1} */
+void sgm_default_census_window(sgm_census_window* w);
+int  sgm_set_census_window(sgm_handle* h, const sgm_census_window* w);
+int  sgm_get_census_window(const sgm_handle* h, sgm_census_window* w);
+/* Validate a window without a handle (0 = a census match would accept it). Host-only.          */
+int  sgm_check_census_window(const sgm_census_window* w);
+/* The window of a correlation_window_size slider value (cfg/i3DR_Disparity.cfg), the one table
+ * the adapters use: w|1 <= 3: {3,3,1}; 5: {5,5,1}; 7: {7,7,1}; 9: {9,7,1}; 11, 13: {7,7,2};
+ * >= 15: {9,7,2} (even values count as the next odd one). Host-only.                           */
+int  sgm_census_window_from_size(int w, sgm_census_window* out);
 
 /* ---- hole filling ------------------------------------------------------------------------- */
 /* The post filter behind the node's `interp` knob (cfg/i3DR_Disparity.cfg:39, "will smooth
@@ -520,12 +560,14 @@ int  sgm_node_frame(sgm_handle* h, const sgm_camera_info* left, const sgm_camera
 int  sgm_node_frame_map_builds(const sgm_handle* h);
 
 /* ---- stage entry points (parity tests compare each stage with the CPU oracle) ----------- */
-/* 9x7 census codes of one image (host buffers; out: W x H uint64, row-major).             */
+/* Census codes of one image under the handle's window, 9x7 by default (host buffers; out:
+ * W x H uint64, row-major). An invalid window is SGM_ERR_PARAM in the census mode; in the
+ * OCV and BM modes, which ignore the window, it gives the 9x7 codes.                       */
 int  sgm_debug_census(sgm_handle* h, const uint8_t* img, int width, int height,
                       size_t stride, uint64_t* out);
 /* Census mode: u8 path-cost volume of direction `dir` (0..7; see DESIGN.md for the order),
  * layout [H][width1][D]. Runs census + that direction only (a direction, not a path set:
- * sgm_set_census_paths does not change it).                                                */
+ * sgm_set_census_paths does not change it), with the handle's census window.               */
 int  sgm_debug_census_path(sgm_handle* h, const uint8_t* left, const uint8_t* right,
                            int width, int height, size_t stride, int dir, uint8_t* vol);
 /* OCV modes: int16 aggregated matching cost C' = SAD + P2 used by the path recurrence,
