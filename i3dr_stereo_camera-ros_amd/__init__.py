@@ -171,6 +171,7 @@ EXPORTS = [
     "sgm_fill_holes", "sgm_debug_fill",
     "sgm_default_census_window", "sgm_set_census_window", "sgm_get_census_window", "sgm_check_census_window",
     "sgm_census_window_from_size",
+    "sgm_debug_bm_plan",
 ]
 
 
@@ -380,6 +381,9 @@ def load_library(path=None):
     L.sgm_get_census_window.argtypes = [vp, P(CensusWindow)]
     L.sgm_check_census_window.argtypes = [P(CensusWindow)]
     L.sgm_census_window_from_size.argtypes = [ci, P(CensusWindow)]
+    if not hasattr(L, "sgm_debug_bm_plan"):
+        raise ImportError(f"{path}: sgm_debug_bm_plan is missing: rebuild the library")
+    L.sgm_debug_bm_plan.argtypes = [P(SgmParams), P(BmParams), ci, ci, ci, P(ci * 12)]
     _lib = L
     return L
 
@@ -415,6 +419,21 @@ def bm_geometry(params, width, height):
     x0, x1 = max(D - 1 + minD, 0), min(width, width + minD)
     w1 = 0 if (x0 >= width or x1 <= 0 or x1 <= x0) else x1 - x0
     return dict(X0=x0, X1=x1, width1=w1, D=D, invalid=(minD - 1) * 16)
+
+
+BM_PLAN_FIELDS = ("TX", "nsx", "nsy", "RB", "waves", "lds", "vglobal", "wide", "nk", "Dp", "width1", "rows")
+
+
+def bm_plan(params, bm_params, width, height, n_cu):
+    """sgm_debug_bm_plan: the tiling of the fused MODE_OCV_BM kernel for a width x height frame on
+    a device of n_cu compute units, as a dict of BM_PLAN_FIELDS (host-only, needs no device).
+    SGM_BM_VGLOBAL applies as at a match."""
+    out = (ctypes.c_int * 12)()
+    rc = load_library().sgm_debug_bm_plan(ctypes.byref(params), ctypes.byref(bm_params), int(width), int(height),
+                                          int(n_cu), ctypes.byref(out))
+    if rc != SGM_OK:
+        raise SGMError(rc, "sgm_debug_bm_plan")
+    return dict(zip(BM_PLAN_FIELDS, out))
 
 
 def device_count():

@@ -283,6 +283,20 @@ int sgm_debug_path_items(const sgm_params* p, int width, int height, unsigned di
     return sgm::census_path_items(g, dir_mask & 0xFFu, n_slots, group, out, cap, up_group);
 }
 
+int sgm_debug_bm_plan(const sgm_params* p, const sgm_bm_params* bm, int width, int height, int n_cu, int out[12])
+{
+    if (!p || !bm || !out || p->mode != SGM_MODE_OCV_BM) return SGM_ERR_ARG;
+    Geom g;
+    std::string err;
+    const int rc = make_geom(*p, width, height, g, err, bm);
+    if (rc) return rc;
+    const sgm::BmPlan pl = sgm::bm_plan(g, n_cu);
+    const int v[12] = {pl.TX, pl.nsx, pl.nsy, pl.RB, pl.waves, (int)pl.lds, pl.vglobal, pl.wide, pl.nk, pl.Dp,
+                       g.width1, std::max(g.H - 2 * g.SW2, 0)};
+    std::copy(v, v + 12, out);
+    return SGM_OK;
+}
+
 int sgm_debug_speckle(sgm_handle* h, int16_t* disp, int W, int H, int new_val, int max_size, int max_diff)
 {
     return debug_post(h, disp, W, H, 1, new_val, max_size, max_diff);

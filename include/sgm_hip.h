@@ -584,6 +584,22 @@ int  sgm_debug_bm_prefilter(sgm_handle* h, const uint8_t* img, int width, int he
  * Either output may be NULL. SGM_ERR_UNSUPPORTED above 2^27 volume cells.                  */
 int  sgm_debug_bm_sad(sgm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
                       size_t stride, int32_t* sad, int32_t* texture);
+/* BM mode: the tiling of the fused SAD + WTA kernel that a match of a width x height frame
+ * takes on a device of n_cu compute units (host-only, no handle, no device). The environment
+ * override of a match applies: SGM_BM_VGLOBAL=1 (column sums in the workspace). out[] in this
+ * order:
+ *    0 TX       output columns of a workgroup's strip     6 vglobal  1: column sums in HBM
+ *    1 nsx      strips (grid x)                           7 wide     1: u32 column sums, 0: u16
+ *    2 nsy      bands (grid y)                            8 nk       64-disparity chunks per lane
+ *    3 RB       output rows of a band                     9 Dp       padded disparities, 64 * nk
+ *    4 waves    waves of a workgroup (8 or 16)           10 width1   computed columns X1 - X0
+ *    5 lds      dynamic LDS bytes of a workgroup         11 rows     computed rows H - 2 * (w / 2)
+ * Returns 0, or the parameter error a match would return (SGM_ERR_ARG for a null pointer or a
+ * mode other than SGM_MODE_OCV_BM). A frame without a computed column (width1 0) is planned as
+ * one of a single column, as make_layout does. Added under ABI version 5 (no existing struct
+ * or signature changed): callers check for the symbol.                                      */
+int  sgm_debug_bm_plan(const sgm_params* p, const sgm_bm_params* bm, int width, int height, int n_cu,
+                       int out[12]);
 /* Census mode: the path work list one launch would dispatch (host-only, no device): every
  * 16-line block of the directions in dir_mask (bit d) of `group` frames, plus the up+WTA
  * blocks (code 8) of `up_group` frames, as dir << 24 | frame << 22 | block, longest first,
