@@ -1,8 +1,12 @@
 """CPU tests of the MODE_OCV_BM tiling (csrc/bm.hip bm_plan) through sgm_debug_bm_plan, which needs
 no device: invariants of the plan over a seeded sweep, the plans of the production frames pinned at
-256 CUs, and the entry point's errors. No GPU test compares these production tilings with the numpy
-reference yet: on a 256-CU device every frame that reference can afford is planned with strips of at
-most 32 columns (asserted below), and the suite has no way to plan a small frame like a large one."""
+256 CUs, and the entry point's errors. On a 256-CU device every frame the explicit-sum reference
+(tests/bm_reference.py) can afford is planned with strips of at most 32 columns (asserted below). The
+box-sum reference (tests/bm_fast_reference.py) affords frames that such a device plans like production
+frames by itself; they and their pinned plans are in tests/bm_tiling_cases.py and
+tests/test_bm_fast_reference.py. No GPU test in the suite compares those tilings yet (BM
+section, says where that stands); bands longer than 41 rows and the full-size frames pinned here are
+compared by nothing."""
 import ctypes
 
 import numpy as np
@@ -111,9 +115,10 @@ def test_production_plans_are_pinned(pkg, monkeypatch, frame, expect):
 
 
 def test_small_frames_never_plan_wide_strips(pkg, monkeypatch):
-    """The gap this file documents: at 256 CUs a frame of up to 2.5 M volume cells (about 10 s of the
-    numpy reference) is never planned with a strip wider than 32 columns, while the production frames
-    above get 102 to 120."""
+    """Why the explicit-sum reference cannot reach the production tilings: at 256 CUs a frame of up to
+    2.5 M volume cells (about 10 s of tests/bm_reference.py) is never planned with a strip wider than 32
+    columns, while the production frames above get 102 to 120. The frames of tests/bm_tiling_cases.py
+    (13 M to 484 M cells, for the box-sum reference) are."""
     clean_env(monkeypatch)
     rng = np.random.default_rng(77)
     n = 0
