@@ -144,6 +144,23 @@ def fill_from_env():
     return (FILL_NAMES[parts[0]], int(nums[0]) if len(nums) > 0 else 16, int(nums[1]) if len(nums) > 1 else 2)
 
 
+def pyramid_from_env():
+    """SGM_HIP_PYRAMID = 0 (default) | 1 | scale -> (level, follow_scale), the pyramid level of the
+    adapters (the C++ adapter core reads the same variable). "scale":
+    setDownsampleScale(s) drives the level (s <= 0.5: level 1, else 0). Unset or empty: level 0. Another
+    value warns and means 0, as hip_sgm_core.cpp does."""
+    raw = os.environ.get("SGM_HIP_PYRAMID")
+    v = (raw or "").strip(" \t\n\v\f\r").lower()
+    if v in ("", "0"):
+        return 0, False
+    if v == "1":
+        return 1, False
+    if v == "scale":
+        return 0, True
+    sys.stderr.write(f'SGM_HIP_PYRAMID="{raw}" is not 0 | 1 | scale: pyramid level 0\n')
+    return 0, False
+
+
 def fill_when_from_env():
     """SGM_HIP_FILL_WHEN = always (default) | interp: with "interp" the node's interp flag drives the
     hole filter (and replaces the Q3 right-view result); another value warns and means always."""
@@ -172,6 +189,8 @@ EXPORTS = [
     "sgm_default_census_window", "sgm_set_census_window", "sgm_get_census_window", "sgm_check_census_window",
     "sgm_census_window_from_size",
     "sgm_debug_bm_plan",
+    "sgm_default_pyramid_params", "sgm_set_pyramid_params", "sgm_get_pyramid_params", "sgm_check_pyramid_params",
+    "sgm_pyramid_plan", "sgm_debug_pyr_down", "sgm_debug_pyr_refine",
 ]
 
 
@@ -229,6 +248,18 @@ class CensusWindow(ctypes.Structure):
 
     def as_tuple(self):
         return (self.taps_x, self.taps_y, self.step)
+
+
+class PyramidParams(ctypes.Structure):
+    """`sgm_pyramid_params` of include/sgm_hip.h: level 0 (off) or 1 (half-resolution match refined at
+    full resolution over +-radius disparities, radius 1..2)."""
+    _fields_ = [("level", ctypes.c_int), ("radius", ctypes.c_int)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+PYRAMID_PLAN_FIELDS = ("Wc", "Hc", "mc", "Dc", "invalid_c", "invalid")
 
 
 class CameraInfo(ctypes.Structure):
@@ -384,6 +415,19 @@ def load_library(path=None):
     if not hasattr(L, "sgm_debug_bm_plan"):
         raise ImportError(f"{path}: sgm_debug_bm_plan is missing: rebuild the library")
     L.sgm_debug_bm_plan.argtypes = [P(SgmParams), P(BmParams), ci, ci, ci, P(ci * 12)]
+    # ... and the pyramid entry points
+    for name in ("sgm_default_pyramid_params", "sgm_set_pyramid_params", "sgm_get_pyramid_params",
+                 "sgm_check_pyramid_params", "sgm_pyramid_plan", "sgm_debug_pyr_down", "sgm_debug_pyr_refine"):
+        if not hasattr(L, name):
+            raise ImportError(f"{path}: {name} is missing: rebuild the library")
+    L.sgm_default_pyramid_params.argtypes = [P(PyramidParams)]
+    L.sgm_default_pyramid_params.restype = None
+    L.sgm_set_pyramid_params.argtypes = [vp, P(PyramidParams)]
+    L.sgm_get_pyramid_params.argtypes = [vp, P(PyramidParams)]
+    L.sgm_check_pyramid_params.argtypes = [P(PyramidParams)]
+    L.sgm_pyramid_plan.argtypes = [P(SgmParams), P(BmParams), P(PyramidParams), ci, ci, P(ci * 6)]
+    L.sgm_debug_pyr_down.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
+    L.sgm_debug_pyr_refine.argtypes = [vp, vp, vp, ci, ci, sz, vp, ci, ci, ci, ci, ci, vp]
     _lib = L
     return L
 
@@ -410,6 +454,26 @@ def default_fill_params(**kw):
     for k, v in kw.items():
         setattr(f, k, int(v))
     return f
+
+
+def default_pyramid_params(**kw):
+    y = PyramidParams()
+    load_library().sgm_default_pyramid_params(ctypes.byref(y))
+    for k, v in kw.items():
+        setattr(y, k, int(v))
+    return y
+
+
+def pyramid_plan(params, pyramid, width, height, bm_params=None):
+    """sgm_pyramid_plan: the geometry a match of a width x height frame runs its matcher at, as a
+    dict of PYRAMID_PLAN_FIELDS (host-only, needs no device); raises SGMError with the status a match
+    would return."""
+    out = (ctypes.c_int * 6)()
+    rc = load_library().sgm_pyramid_plan(ctypes.byref(params), ctypes.byref(bm_params) if bm_params is not None else None,
+                                         ctypes.byref(pyramid), int(width), int(height), ctypes.byref(out))
+    if rc != SGM_OK:
+        raise SGMError(rc, "sgm_pyramid_plan")
+    return dict(zip(PYRAMID_PLAN_FIELDS, out))
 
 
 def bm_geometry(params, width, height):
@@ -551,6 +615,48 @@ class Engine:
         f = FillParams()
         self._check(self.lib.sgm_get_fill_params(self.h, ctypes.byref(f)))
         return f
+
+    def set_pyramid_params(self, y):
+        """The pyramid level of every match of this engine (PyramidParams; level 1: a half-resolution
+        match refined at full resolution). Stored as given; bad values fail at match time."""
+        self._check(self.lib.sgm_set_pyramid_params(self.h, ctypes.byref(y)))
+
+    def get_pyramid_params(self):
+        y = PyramidParams()
+        self._check(self.lib.sgm_get_pyramid_params(self.h, ctypes.byref(y)))
+        return y
+
+    def pyramid_plan(self, width, height):
+        """pyramid_plan() of this engine's parameters, BM parameters and pyramid parameters."""
+        return pyramid_plan(self.get_params(), self.get_pyramid_params(), width, height, self.get_bm_params())
+
+    def pyr_down(self, left, right):
+        """sgm_debug_pyr_down: both u8 images halved (2x2 box average, replicate clamping)."""
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        if left.ndim != 2 or left.shape != right.shape:
+            raise ValueError("left/right must be equal-size 2-D u8 images")
+        h, w = left.shape
+        ol = np.empty(((h + 1) // 2, (w + 1) // 2), np.uint8)
+        orr = np.empty_like(ol)
+        self._check(self.lib.sgm_debug_pyr_down(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(ol), _ptr(orr)))
+        return ol, orr
+
+    def pyr_refine(self, left, right, coarse, m, D, mc, radius=2, subpixel=True):
+        """sgm_debug_pyr_refine: the level-1 refinement of a coarse int16 image on the full-resolution
+        pair (m, D: the full-resolution range; mc: the coarse minimum)."""
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        coarse = np.ascontiguousarray(coarse, np.int16)
+        if left.ndim != 2 or left.shape != right.shape:
+            raise ValueError("left/right must be equal-size 2-D u8 images")
+        h, w = left.shape
+        if coarse.shape != ((h + 1) // 2, (w + 1) // 2):
+            raise ValueError("coarse must be the ((h + 1) // 2, (w + 1) // 2) int16 image")
+        out = np.empty((h, w), np.int16)
+        self._check(self.lib.sgm_debug_pyr_refine(self.h, _ptr(left), _ptr(right), w, h, w, _ptr(coarse), int(m), int(D),
+                                                  int(mc), int(radius), 1 if subpixel else 0, _ptr(out)))
+        return out
 
     def fill_holes(self, d_src, src_stride, width, height, invalid, params, rect, d_dst, dst_stride, stream=None):
         """sgm_fill_holes on device pointers (int16 images, strides in elements): the holes of
@@ -1066,6 +1172,8 @@ class MatcherHIPSGM:
         self.fill_when = fill_when_from_env()
         # census mode: the census window; with SGM_HIP_CENSUS_WINDOW=cfg setWindowSize drives it
         self.census_window, self.census_window_cfg = census_window_from_env()
+        # SGM_HIP_PYRAMID: the pyramid level; with "scale" setDownsampleScale drives it
+        self.pyramid_level, self.pyramid_scale = pyramid_from_env()
         self.init()
 
     # --- AbstractStereoMatcher ----------------------------------------------------------
@@ -1099,7 +1207,16 @@ class MatcherHIPSGM:
         self.image_size = (self.left.shape[1], self.left.shape[0])
 
     def setDownsampleScale(self, scale=1.0):
+        # no CPU resize ever happens: under SGM_HIP_PYRAMID=scale a scale <= 0.5 selects pyramid level 1
+        # (the engine halves the pair on the device), otherwise the value is stored and ignored
         self.downsample_scale = scale
+        if self.pyramid_scale:
+            self.pyramid_level = 1 if scale <= 0.5 else 0
+
+    def setPyramidLevel(self, level):
+        """The pyramid level of every match (0, or 1: half-resolution match refined at full
+        resolution); stored as given, another value fails at match time."""
+        self.pyramid_level = int(level)
 
     def setDisparityRange(self, disparity_range):
         if disparity_range <= 0:
@@ -1185,6 +1302,7 @@ class MatcherHIPSGM:
         eng.set_census_paths(self.census_paths)
         eng.set_census_window(*self.census_window)
         eng.set_fill_params(self.effective_fill())
+        eng.set_pyramid_params(default_pyramid_params(level=self.pyramid_level))
         # colour frames: COLOR_BGR2GRAY on the device, with the grey set of the OpenCV release the
         # compat bits name (COL0_LEGACY marks 3.x: Y14; otherwise 4.x: Y15)
         eng.set_raw_format(3 if np.ndim(a) == 3 else 1,
@@ -1390,6 +1508,7 @@ def image_cb(matcher, left_raw, right_raw, info_left, info_right, f, T, depth_mi
         eng.set_census_paths(matcher.census_paths)
         eng.set_census_window(*matcher.census_window)
         eng.set_fill_params(matcher.effective_fill())
+        eng.set_pyramid_params(default_pyramid_params(level=matcher.pyramid_level))
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm)
@@ -1444,6 +1563,7 @@ def image_cb_host(matcher, left_raw, right_raw, info_left, info_right, f, T, dep
         eng.set_census_paths(matcher.census_paths)
         eng.set_census_window(*matcher.census_window)
         eng.set_fill_params(matcher.effective_fill())
+        eng.set_pyramid_params(default_pyramid_params(level=matcher.pyramid_level))
         eng.set_raw_format(ch, GRAY_Y14 if (params.ocv_compat & OCV_COL0_LEGACY) else GRAY_Y15)
         if params.mode == MODE_OCV_BM:
             eng.set_bm_params(bm)

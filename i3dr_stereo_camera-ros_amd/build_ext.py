@@ -19,7 +19,7 @@ ARCH = "gfx950"
 
 # the slowest first: the pool starts them in list order
 SOURCES = ["census_sgm.hip", "ocv_sgm.hip", "ocv_cost.hip", "bm.hip", "post.hip", "fill.hip", "depth.hip", "rectify.hip",
-           "census_win.hip", "sgm_plan.cpp", "sgm_pipeline.cpp", "sgm_api.cpp", "sgm_node.cpp", "sgm_batch_io.cpp", "sgm_tiled.cpp", "sgm_debug.cpp"]
+           "census_win.hip", "pyramid.hip", "sgm_plan.cpp", "sgm_pipeline.cpp", "sgm_api.cpp", "sgm_node.cpp", "sgm_batch_io.cpp", "sgm_tiled.cpp", "sgm_debug.cpp", "sgm_pyramid.cpp"]
 HEADERS = ["sgm_device.h", "ocv_device.h", "sgm_launch.h", "sgm_host.h"]
 
 

@@ -254,6 +254,7 @@ void sgm_destroy(sgm_handle* h)
         if (h->node_ev) (void)hipEventDestroy(h->node_ev);
         if (h->node_maps) (void)hipFree(h->node_maps);
         if (h->node_buf) (void)hipFree(h->node_buf);
+        if (h->pyr_buf) (void)hipFree(h->pyr_buf);
         for (const auto& r : h->regs) (void)hipHostUnregister(r.host);
         if (h->done) (void)hipEventDestroy(h->done);
         if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -329,7 +330,8 @@ int sgm_match_device(sgm_handle* h, const uint8_t* dL, const uint8_t* dR, int W,
                      size_t out_stride, void* stream)
 {
     if (!h) return SGM_ERR_ARG;
-    if (h->rect_on) {          // raw inputs: rectified in the census tiles or by the OCV / BM pre-pass
+    // raw inputs: rectified in the census tiles or by the OCV / BM pre-pass; pyramid level 1: a batch of one
+    if (h->rect_on || pyramid_on(h->cfg)) {
         const uint8_t* l1[1] = {dL};
         const uint8_t* r1[1] = {dR};
         int16_t* o1[1] = {dOut};
@@ -366,6 +368,17 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
     for (int i = 0; i < n; i++)
         if (!dLs[i] || !dRs[i] || !outs[i]) return fail(h, SGM_ERR_ARG, "null frame pointer");
     if (n == 0) return SGM_OK;
+    return device_batch_locked(h, dLs, dRs, n, W, H, stride, rectLs, rectRs, rect_stride, outs, out_stride, stream);
+}
+
+}  // extern "C"
+
+int sgm::device_batch_locked(sgm_handle* h, const uint8_t* const* dLs, const uint8_t* const* dRs, int n, int W, int H,
+                             size_t stride, uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride,
+                             int16_t* const* outs, size_t out_stride, void* stream)
+{
+    if (pyramid_on(h->cfg))
+        return pyr_device_batch(h, dLs, dRs, n, W, H, stride, rectLs, rectRs, rect_stride, outs, out_stride, stream);
     Geom g;
     Layout l;
     int rc = make_geom(h->cfg.params, W, H, g, h->err, &h->cfg.bm);
@@ -399,6 +412,8 @@ int sgm_match_device_batch_rect(sgm_handle* h, const uint8_t* const* dLs, const 
     h->stream = own;
     return rc;
 }
+
+extern "C" {
 
 int sgm_match_device_batch(sgm_handle* h, const uint8_t* const* dLs, const uint8_t* const* dRs, int n, int W, int H,
                            size_t stride, int16_t* const* outs, size_t out_stride, void* stream)
@@ -575,6 +590,7 @@ int sgm_match(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, s
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification applies to device-buffer matches");
     if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W * raw_bpp(h) || out_stride < (size_t)W)
         return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
+    if (pyramid_on(h->cfg)) return pyr_match_host(h, L, R, W, H, stride, disp, out_stride, false);
     return match_host(h, L, R, W, H, stride, disp, out_stride, false);
 }
 
@@ -586,6 +602,7 @@ int sgm_match_f32(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int 
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification applies to device-buffer matches");
     if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W * raw_bpp(h) || out_stride < (size_t)W)
         return fail(h, SGM_ERR_ARG, "bad buffers or sizes");
+    if (pyramid_on(h->cfg)) return pyr_match_host(h, L, R, W, H, stride, disp, out_stride, true);
     return match_host(h, L, R, W, H, stride, disp, out_stride, true);
 }
 

@@ -344,6 +344,7 @@ int sgm_match_batch(sgm_handle* h, const uint8_t* const* lefts, const uint8_t* c
     if (!h || !lefts || !rights || !disps || n_frames < 0) return SGM_ERR_ARG;
     if (W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W) return fail(h, SGM_ERR_ARG, "bad sizes");
     if (int rf = refuse_colour(h, "sgm_match_batch")) return rf;
+    if (int rf = refuse_pyramid(h, "sgm_match_batch")) return rf;
     for (int i = 0; i < n_frames; i++)
         if (!lefts[i] || !rights[i] || !disps[i]) return fail(h, SGM_ERR_ARG, "null frame pointer");
     if (n_frames == 0) return SGM_OK;

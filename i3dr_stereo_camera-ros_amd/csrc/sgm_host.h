@@ -4,7 +4,8 @@
 //   sgm_plan.cpp      decides without touching the device: geometry, workspace layouts, knobs
 //   sgm_pipeline.cpp  the handle's resources, the frame pipelines and batch schedulers (uses plan)
 //   sgm_api.cpp       create / destroy / set / get, the match and standalone kernel entry points
-//   sgm_node.cpp      sgm_node_frame: the node's imageCb on host buffers (uses pipeline)
+//   sgm_pyramid.cpp   pyramid level 1 around the level-0 entry points of sgm_api.cpp (uses pipeline)
+//   sgm_node.cpp      sgm_node_frame: the node's imageCb on host buffers (uses pipeline, pyramid)
 //   sgm_batch_io.cpp  per-device sub-handles and the host streaming ring of sgm_match_batch
 //   sgm_tiled.cpp     the two multi-device tile modes (uses open_subs / run_on_subs of batch_io)
 //   sgm_debug.cpp     profiling and the sgm_debug_* stage entry points
@@ -31,6 +32,8 @@ inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 constexpr sgm_bm_params kBmDefaults = {10, 9};   // texture_threshold, prefilter_size
 constexpr sgm_fill_params kFillDefaults = {SGM_FILL_OFF, 16, 2};   // mode, max_gap, min_neighbours
 constexpr sgm_census_window kCensusWindowDefault = {9, 7, 1};     // taps_x, taps_y, step
+constexpr sgm_pyramid_params kPyramidDefaults = {0, 2};           // level, radius
+constexpr int kPyrGroup = 8;           // frames of a level-1 batch whose planes exist at once
 
 // What a handle matches with: the setters write it, every sub-handle family receives it whole.
 struct MatchConfig {
@@ -41,7 +44,9 @@ struct MatchConfig {
     int gray_set = SGM_GRAY_Y14;      // ... and the COLOR_BGR2GRAY coefficient set used with 3
     sgm_fill_params fill = kFillDefaults;   // sgm_set_fill_params: the hole-filling post filter
     sgm_census_window cwin = kCensusWindowDefault;   // SGM_MODE_CENSUS8 only (sgm_set_census_window)
+    sgm_pyramid_params pyr = kPyramidDefaults;       // sgm_set_pyramid_params: level 1 = coarse match + refinement
 };
+inline bool pyramid_on(const MatchConfig& c) { return c.pyr.level != 0; }
 inline bool fill_on(const MatchConfig& c) { return c.fill.mode != SGM_FILL_OFF; }
 // the census runs as its own launch on 8UC1 planes (census_win.hip): the census mode with a
 // window other than the default
@@ -128,6 +133,10 @@ struct sgm_handle {
     char* node_buf = nullptr;
     size_t node_buf_size = 0;
     hipEvent_t node_ev = nullptr;
+    // pyramid level 1: the planes of a group of frames (grey, coarse images, code planes, coarse
+    // disparity, the image in front of the hole filter) and the host entry points' staging
+    char* pyr_buf = nullptr;
+    size_t pyr_buf_size = 0;
 };
 
 namespace sgm {
@@ -288,6 +297,25 @@ int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geo
             bool rect = false);
 int match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, size_t stride, void* out,
                size_t out_stride, bool f32);
+
+int config_status(sgm_handle* h, const MatchConfig& c);
+
+// sgm_api.cpp: sgm_match_device_batch_rect with h->mu already held and the buffers checked
+int device_batch_locked(sgm_handle* h, const uint8_t* const* dLs, const uint8_t* const* dRs, int n, int W, int H,
+                        size_t stride, uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride,
+                        int16_t* const* outs, size_t out_stride, void* stream);
+
+// sgm_pyramid.cpp: level 1 (h->mu held by the caller, buffers checked)
+struct PyrPlan { int Wc, Hc, mc, Dc, invalid_c, invalid; };
+int pyramid_status(const sgm_pyramid_params& p, std::string& err);
+int pyramid_plan(const MatchConfig& c, int W, int H, PyrPlan& pl, MatchConfig& coarse, std::string& err);
+int refuse_pyramid(sgm_handle* h, const char* what);
+int pyr_device_batch(sgm_handle* h, const uint8_t* const* dLs, const uint8_t* const* dRs, int n, int W, int H,
+                     size_t stride, uint8_t* const* rectLs, uint8_t* const* rectRs, size_t rect_stride,
+                     int16_t* const* outs, size_t out_stride, void* stream, bool host_io = false,
+                     hipEvent_t rect_ev = nullptr);
+int pyr_match_host(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, size_t stride, void* out,
+                   size_t out_stride, bool f32);
 
 // sgm_api.cpp: sgm_fill_holes with h->mu already held
 int fill_holes_locked(sgm_handle* h, const int16_t* d_src, size_t src_stride, int W, int H, int invalid,

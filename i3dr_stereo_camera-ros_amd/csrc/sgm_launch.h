@@ -86,6 +86,13 @@ hipError_t launch_ocv_wta(const int16_t* C, const void* vols, size_t cells, int 
                           size_t out_stride, hipStream_t st);
 int ocv_evol_mode(const Geom& g, int dirmask, int skipdir);
 
+// pyramid.hip
+hipError_t launch_pyr_down(const uint8_t* L, const uint8_t* R, size_t stride, int W, int H, uint8_t* Lc, uint8_t* Rc,
+                           uint32_t* KL, uint32_t* KR, hipStream_t st);
+hipError_t launch_pyr_refine(const uint32_t* KL, const uint32_t* KR, const int16_t* coarse, size_t cstride, int W,
+                             int H, int m, int D, int mc, int radius, int subpixel, int16_t* out, size_t ostride,
+                             hipStream_t st);
+
 // bm.hip
 hipError_t launch_bm_prefilter(const uint8_t* L, const uint8_t* R, size_t stride, int W, int H, int cap, uint8_t* PL,
                                uint8_t* PR, hipStream_t st);

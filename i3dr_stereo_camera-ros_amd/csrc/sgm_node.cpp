@@ -71,13 +71,24 @@ int node_frame(sgm_handle* h, const sgm_camera_info& cl, const sgm_camera_info& 
     if (rc || (rc = check_camera(h, cr, ir[1]))) return rc;
     Geom g;
     Layout l;
-    if ((rc = make_geom(h->cfg.params, W, H, g, h->err, &h->cfg.bm))) return rc;
-    if (g.width1 <= 0) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
     const sgm_params& p = h->cfg.params;
     const bool census = p.mode == SGM_MODE_CENSUS8;
-    // the pre-pass into the grey planes: the OCV / BM modes, and the census with a non-default window
-    if ((rc = prepare(h, h->cfg, W, H, false, g, l, census ? batch_group(1) : 0, !census || census_win_on(h->cfg))))
-        return rc;
+    // pyramid level 1: the level-1 batch of one raw frame does the matching (its own checks, first)
+    const bool pyr = pyramid_on(h->cfg);
+    if (pyr) {
+        PyrPlan pl;
+        MatchConfig coarse;
+        if ((rc = pyramid_plan(h->cfg, W, H, pl, coarse, h->err)) || (rc = config_status(h, h->cfg))) return rc;
+        if (W + std::min(p.min_disparity, 0) - std::max(p.min_disparity + p.num_disparities, 0) <= 0)
+            return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
+        if ((rc = ensure_stream(h))) return rc;
+    } else {
+        if ((rc = make_geom(h->cfg.params, W, H, g, h->err, &h->cfg.bm))) return rc;
+        if (g.width1 <= 0) return fail(h, SGM_ERR_UNSUPPORTED, "fused rectification needs a non-empty disparity window");
+        // the pre-pass into the grey planes: the OCV / BM modes, and the census with a non-default window
+        if ((rc = prepare(h, h->cfg, W, H, false, g, l, census ? batch_group(1) : 0, !census || census_win_on(h->cfg))))
+            return rc;
+    }
     if ((rc = ensure_cubic_table(h))) return rc;
     hipStream_t st = h->stream;
     if (!h->cpy) HIP_TRY(hipStreamCreateWithFlags(&h->cpy, hipStreamNonBlocking), "hipStreamCreate");
@@ -147,7 +158,7 @@ int node_frame(sgm_handle* h, const sgm_camera_info& cl, const sgm_camera_info& 
     // outputs inside a registered range go through their mapping
     char* mDisp = mapped(h, io.disparity, io.disparity_stride * 4 * (size_t)(H - 1) + (size_t)W * 4);
     char* mDepth = io.depth ? mapped(h, io.depth, io.depth_stride * 4 * (size_t)(H - 1) + (size_t)W * 4) : nullptr;
-    const bool wta_rows = census && !use_median(p) && !use_speckle(p) && !l.fill && mDisp;
+    const bool wta_rows = !pyr && census && !use_median(p) && !use_speckle(p) && !l.fill && mDisp;
     const float qf[5] = {io.q5 ? (float)io.q5[0] : 0.f, io.q5 ? (float)io.q5[1] : 0.f, io.q5 ? (float)io.q5[2] : 0.f,
                          io.q5 ? (float)io.q5[3] : 0.f, io.q5 ? (float)io.q5[4] : 0.f};
 
@@ -158,7 +169,15 @@ int node_frame(sgm_handle* h, const sgm_camera_info& cl, const sgm_camera_info& 
         h->rect_on = true;
         uint8_t* rl = io.rect_left ? dRectL : nullptr;
         uint8_t* rr = io.rect_right ? dRectR : nullptr;
-        if (census) {
+        if (pyr) {
+            const uint8_t* l1[1] = {dRawL};
+            const uint8_t* r1[1] = {dRawR};
+            int16_t* o1[1] = {d16};
+            uint8_t* rl1[1] = {rl};
+            uint8_t* rr1[1] = {rr};
+            rc = pyr_device_batch(h, l1, r1, 1, W, H, row, rl ? rl1 : nullptr, rr ? rr1 : nullptr, row, o1, W, nullptr,
+                                  false, want_rect ? h->node_ev : nullptr);
+        } else if (census) {
             NodeOut no;
             no.rect_ev = want_rect ? h->node_ev : nullptr;
             if (wta_rows) {

@@ -562,16 +562,24 @@ size_t raw_bpp(const sgm_handle* h) { return h->cfg.raw_ch == 3 ? 3 : 1; }
 
 // Geometry, layout and workspace of a W x H frame under configuration c (the handle's own, or
 // a copy of it that a debug entry point adjusted).
-int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group, bool rect)
+// what a match checks of a configuration besides the geometry (make_geom)
+int config_status(sgm_handle* h, const MatchConfig& c)
 {
-    int rc = make_geom(c.params, W, H, g, h->err, &c.bm);
-    if (rc) return rc;
+    int rc;
     if (c.params.mode == SGM_MODE_CENSUS8 && c.census_paths != 4 && c.census_paths != 8)
         return fail(h, SGM_ERR_PARAM, "census paths must be 4 or 8 (sgm_set_census_paths), got " +
                                           std::to_string(c.census_paths));
     if (c.params.mode == SGM_MODE_CENSUS8 && (rc = census_window_status(c.cwin, h->err))) return rc;
     if ((rc = raw_format_status(h, c))) return rc;
     if ((rc = fill_params_status(c.fill, h->err))) return rc;
+    return pyramid_status(c.pyr, h->err);
+}
+
+int prepare(sgm_handle* h, const MatchConfig& c, int W, int H, bool host_io, Geom& g, Layout& l, int group, bool rect)
+{
+    int rc = make_geom(c.params, W, H, g, h->err, &c.bm);
+    if (rc) return rc;
+    if ((rc = config_status(h, c))) return rc;
     if ((rc = ensure_stream(h))) return rc;
     l = make_layout(c, g, host_io, group, h->n_cu, rect);
     // the uploaded path work lists live in the workspace: any other use of it invalidates them, also

@@ -53,6 +53,7 @@ int sgm_match_tiled(sgm_handle* h, const uint8_t* L, const uint8_t* R, int W, in
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
     if (int rf = refuse_colour(h, "sgm_match_tiled")) return rf;
+    if (int rf = refuse_pyramid(h, "sgm_match_tiled")) return rf;
     if (int rf = refuse_fill(h, "sgm_match_tiled")) return rf;
     n_bands = std::min(n_bands, H);
     std::vector<int> devs;
@@ -116,6 +117,7 @@ extern "C" int sgm_match_tiled_device(sgm_handle* h, const uint8_t* dL, const ui
         halo < 0)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes, band count or halo");
     if (int rf = refuse_colour(h, "sgm_match_tiled_device")) return rf;
+    if (int rf = refuse_pyramid(h, "sgm_match_tiled_device")) return rf;
     if (int rf = refuse_fill(h, "sgm_match_tiled_device")) return rf;
     if (h->rect_on) return fail(h, SGM_ERR_UNSUPPORTED, "the tile mode takes rectified images");
     n_bands = std::min(n_bands, H);
@@ -477,6 +479,7 @@ int sgm_match_tiled_exact(sgm_handle* h, const uint8_t* L, const uint8_t* R, int
     if (!L || !R || !disp || W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W || n_bands < 1)
         return fail(h, SGM_ERR_ARG, "bad buffers, sizes or band count");
     if (int rf = refuse_colour(h, "sgm_match_tiled_exact")) return rf;
+    if (int rf = refuse_pyramid(h, "sgm_match_tiled_exact")) return rf;
     std::vector<int> devs;
     if (!devices || n_dev <= 0) {
         for (int i = 0; i < sgm_device_count(); i++) devs.push_back(i);

@@ -1,6 +1,6 @@
 """Build the OpenCV-free plugin core (hip_sgm_core.cpp) into lib/libsgm_plugin_core.so and
 its C++ test drivers lib/plugin_core_test, lib/plugin_bm_test, lib/plugin_paths_test,
-lib/plugin_frame_test, lib/plugin_fill_test and lib/plugin_window_test, all linked against lib/libsgm_hip.so with g++.
+lib/plugin_frame_test, lib/plugin_fill_test, lib/plugin_window_test and lib/plugin_pyramid_test, all linked against lib/libsgm_hip.so with g++.
 (matcherHIPSGM.cpp needs OpenCV + the reference headers and is built inside the ROS tree.)"""
 import os
 import subprocess
@@ -55,6 +55,11 @@ def build():
     if _stale(window_drv, deps + [window_src]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
                               [window_src, core_src, "-o", window_drv] + link)
+    pyramid_src = os.path.join(HERE, "plugin_pyramid_test.cpp")
+    pyramid_drv = os.path.join(LIBDIR, "plugin_pyramid_test")
+    if _stale(pyramid_drv, deps + [pyramid_src]):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra"] + inc +
+                              [pyramid_src, core_src, "-o", pyramid_drv] + link)
     return so
 
 

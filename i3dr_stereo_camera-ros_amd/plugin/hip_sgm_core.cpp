@@ -164,8 +164,29 @@ bool fill_when_interp_from_env()
     return false;
 }
 
+// SGM_HIP_PYRAMID = 0 | 1 | scale: the pyramid level of the adapter (sgm_set_pyramid_params). Case
+// and surrounding blanks are ignored. "scale": *follow_scale, setDownsampleScale drives the level.
+// Unset or blank: level 0. Another value gives level 0 and a note on stderr (the Python mirror's
+// pyramid_from_env does the same).
+int pyramid_from_env(bool* follow_scale)
+{
+    if (follow_scale) *follow_scale = false;
+    const char* e = std::getenv("SGM_HIP_PYRAMID");
+    if (!e) return 0;
+    const std::string v = trimmed_lower(e);
+    if (v.empty() || v == "0") return 0;
+    if (v == "1") return 1;
+    if (v == "scale") {
+        if (follow_scale) *follow_scale = true;
+        return 0;
+    }
+    std::cerr << "SGM_HIP_PYRAMID=\"" << e << "\" is not 0 | 1 | scale: pyramid level 0" << std::endl;
+    return 0;
+}
+
 MatcherCore::MatcherCore(int device, int mode) : device_(device)
 {
+    pyramid_level_ = pyramid_from_env(&pyramid_scale_);
     census_paths_ = census_paths_from_env(8);
     census_window_ = census_window_from_env(&census_window_cfg_);
     fill_ = fill_from_env();
@@ -244,6 +265,12 @@ void MatcherCore::setCensusWindow(int taps_x, int taps_y, int step) { census_win
 void MatcherCore::setCensusWindowFollowsSize(bool follow) { census_window_cfg_ = follow; }
 void MatcherCore::setHoleFilling(int mode, int max_gap, int min_neighbours) { fill_ = sgm_fill_params{mode, max_gap, min_neighbours}; }
 void MatcherCore::setFillWhenInterp(bool interp) { fill_when_interp_ = interp; }
+void MatcherCore::setPyramidLevel(int level) { pyramid_level_ = level; }
+void MatcherCore::setPyramidFollowsScale(bool follow) { pyramid_scale_ = follow; }
+void MatcherCore::setDownsampleScale(double scale)
+{
+    if (pyramid_scale_) pyramid_level_ = scale <= 0.5 ? 1 : 0;
+}
 sgm_fill_params MatcherCore::effectiveFill() const
 {
     sgm_fill_params f = fill_;
@@ -289,6 +316,10 @@ int MatcherCore::run(const sgm_params& p, const sgm_bm_params& bm, const uint8_t
     if (rc == SGM_OK) rc = sgm_set_census_window(handle_, &census_window_);
     const sgm_fill_params fill = effectiveFill();
     if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
+    sgm_pyramid_params pyr;
+    sgm_default_pyramid_params(&pyr);
+    pyr.level = pyramid_level_;
+    if (rc == SGM_OK) rc = sgm_set_pyramid_params(handle_, &pyr);
     if (rc == SGM_OK && keep_reg_ && outf) {
         const size_t bytes = out_stride * sizeof(float) * (size_t)(h - 1) + (size_t)w * sizeof(float);
         if (reg_ptr_ != (void*)outf || reg_bytes_ != bytes) {
@@ -354,6 +385,10 @@ int MatcherCore::imageCb(const uint8_t* raw_left, const uint8_t* raw_right, int 
     if (rc == SGM_OK) rc = sgm_set_census_paths(handle_, census_paths_);
     if (rc == SGM_OK) rc = sgm_set_census_window(handle_, &census_window_);
     if (rc == SGM_OK) rc = sgm_set_fill_params(handle_, &fill);
+    sgm_pyramid_params pyr;
+    sgm_default_pyramid_params(&pyr);
+    pyr.level = pyramid_level_;
+    if (rc == SGM_OK) rc = sgm_set_pyramid_params(handle_, &pyr);
     // colour frames: the grey set of the OpenCV release the compat bits name (COL0_LEGACY marks 3.x)
     if (rc == SGM_OK)
         rc = sgm_set_raw_format(handle_, channels, (p.ocv_compat & SGM_OCV_COL0_LEGACY) ? SGM_GRAY_Y14 : SGM_GRAY_Y15);

@@ -29,6 +29,9 @@ sgm_census_window census_window_from_env(bool* follow_cfg);
 sgm_fill_params fill_from_env();
 // SGM_HIP_FILL_WHEN (always | interp): true for interp; anything else (with a note) is always
 bool fill_when_interp_from_env();
+// SGM_HIP_PYRAMID (0 | 1 | scale): the pyramid level; *follow_scale: setDownsampleScale drives it
+// (scale). Unset, blank or unparsable (with a note on stderr): level 0 and no following.
+int pyramid_from_env(bool* follow_scale);
 
 class MatcherCore {
 public:
@@ -72,6 +75,16 @@ public:
     // and in imageCb, and setInterpolation(false) returns it unfilled.
     void setHoleFilling(int mode, int max_gap = 16, int min_neighbours = 2);
     void setFillWhenInterp(bool interp);
+    // The pyramid level of every match (sgm_set_pyramid_params with the default radius; default:
+    // the SGM_HIP_PYRAMID env var, else 0). Stored as given: a level other than 0 or 1 fails at
+    // match time. Level 1 matches at half resolution on the device and refines at full resolution;
+    // forward and backward matches and imageCb all use it. With SGM_HIP_PYRAMID=scale (or
+    // setPyramidFollowsScale(true)) setDownsampleScale(s) drives it: s <= 0.5 selects level 1, any
+    // other scale level 0; otherwise setDownsampleScale changes nothing (the node calls it with 1
+    // on every frame). No CPU resize ever happens.
+    void setPyramidLevel(int level);
+    void setPyramidFollowsScale(bool follow);
+    void setDownsampleScale(double scale);
     sgm_fill_params effectiveFill() const;
     bool q3() const { return interpolate_ && !fill_when_interp_; }
     // cv::StereoBM only (SGM_MODE_OCV_BM); stored but unused in the other modes, where the
@@ -126,6 +139,8 @@ public:
     const sgm_census_window& censusWindow() const { return census_window_; }
     bool censusWindowFollowsSize() const { return census_window_cfg_; }
     const sgm_fill_params& holeFilling() const { return fill_; }
+    int pyramidLevel() const { return pyramid_level_; }
+    bool pyramidFollowsScale() const { return pyramid_scale_; }
     const std::string& lastError() const { return err_; }
     // SGBM modes: cv::ximgproc::createRightMatcher of a StereoSGBM. BM mode: of a StereoBM —
     // minD' = -(minD + D) + 1, same D and window, uniqueness 0, no speckle filter, and (through
@@ -146,6 +161,8 @@ private:
     bool census_window_cfg_ = false;   // setWindowSize drives census_window_
     sgm_fill_params fill_{};
     bool fill_when_interp_ = false;
+    int pyramid_level_ = 0;
+    bool pyramid_scale_ = false;       // setDownsampleScale drives pyramid_level_
     bool interpolate_ = false;
     bool keep_reg_ = false;
     void* reg_ptr_ = nullptr;        // the registered output range

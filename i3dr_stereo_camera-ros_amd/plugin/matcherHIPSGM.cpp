@@ -110,6 +110,14 @@ void MatcherHIPSGM::setHoleFilling(int mode, int max_gap, int min_neighbours)
 
 void MatcherHIPSGM::setCensusWindow(int taps_x, int taps_y, int step) { core_.setCensusWindow(taps_x, taps_y, step); }
 
+void MatcherHIPSGM::setPyramidLevel(int level) { core_.setPyramidLevel(level); }
+
+void MatcherHIPSGM::setDownsampleScale(double scale)
+{
+  // downsample_scale stays 1 (setImages copies); the core may take the scale as a pyramid level
+  core_.setDownsampleScale(scale);
+}
+
 void MatcherHIPSGM::setInterpolation(bool enable)
 {
   this->interpolate = enable;

@@ -51,6 +51,13 @@ public:
   // SGM_HIP_CENSUS_WINDOW=cfg, setWindowSize (the node's correlation_window_size slider) drives it
   // through sgm_census_window_from_size (hip_sgm_core.h setCensusWindow).
   void setCensusWindow(int taps_x, int taps_y, int step = 1);
+  // The pyramid level (default: env SGM_HIP_PYRAMID, else 0): 1 matches at half resolution on the
+  // device and refines at full resolution (hip_sgm_core.h setPyramidLevel). With
+  // SGM_HIP_PYRAMID=scale, setDownsampleScale(s) drives it (s <= 0.5: level 1, else 0); without, the
+  // node's per-frame setDownsampleScale(1) changes nothing. The base class's scale stays 1 either
+  // way: setImages never resizes on the CPU.
+  void setPyramidLevel(int level);
+  void setDownsampleScale(double scale);
 
   // cv::StereoBM parameters: used in BM mode, ignored by the SGM modes (matcherOpenCVSGBM.h:31-34)
   void setTextureThreshold(int threshold);

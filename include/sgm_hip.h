@@ -42,7 +42,8 @@ extern "C" {
  * caller that needs them checks for the symbols. The colour entry points (sgm_bgr2gray,
  * sgm_remap_cubic_c3, sgm_set_raw_format, sgm_get_raw_format) came the same way, and so did
  * sgm_node_frame / sgm_node_frame_map_builds with their two structs, and the census window
- * entry points (sgm_*_census_window*) with sgm_census_window.                               */
+ * entry points (sgm_*_census_window*) with sgm_census_window, and the pyramid entry points
+ * (sgm_*_pyramid_params, sgm_pyramid_plan, sgm_debug_pyr_*) with sgm_pyramid_params.           */
 #define SGM_ABI_VERSION 5
 int  sgm_abi_version(void);
 
@@ -266,6 +267,73 @@ int  sgm_check_fill_params(const sgm_fill_params* p);
 int  sgm_fill_holes(sgm_handle* h, const int16_t* d_src, size_t src_stride, int width, int height, int invalid,
                     const sgm_fill_params* params, int x0, int y0, int x1, int y1, int16_t* d_dst,
                     size_t dst_stride, void* stream);
+
+/* ---- half-resolution pyramid level --------------------------------------------------------- */
+/* Coarse-to-fine matching with one coarse level, per handle: the pair is halved, the handle's mode
+ * matches the coarse pair over half the disparity range, and a refinement kernel brings the result
+ * back to full resolution on census codes of the full-resolution images. A quarter of the pixels
+ * times half the disparities is about an eighth of the matching work, and the census mode reaches
+ * num_disparities up to 1024 (its 512 cap applies to the coarse range). Specified by this project
+ * (the I3DR matcher the census mode stands in for is a closed coarse-to-fine matcher);
+ * tests/pyramid_reference.py is the executable statement. Level 0 (the default) is a plain match:
+ * same launches, stage names, workspace and results. Level 1, for a W x H frame with
+ * m = min_disparity and D = num_disparities:
+ *   1. coarse geometry: Wc = (W + 1) >> 1, Hc = (H + 1) >> 1, mc = m >> 1 (arithmetic shift),
+ *      Dc = 16 * ceil((((m + D - 1) >> 1) - mc + 1) / 16).
+ *   2. down: Ic(xc, yc) = (I(x0,y0) + I(x1,y0) + I(x0,y1) + I(x1,y1) + 2) >> 2 with x0 = 2 xc,
+ *      x1 = min(2 xc + 1, W - 1), likewise for y, on both 8UC1 images (profiling stage `pyr_down`).
+ *      Colour and raw frames first go through the pre-pass of the OCV modes into full-resolution
+ *      grey planes (stage `gray`, or `rectify`, which writes the requested rectified images
+ *      unchanged), in every mode.
+ *   3. coarse match: exactly a level-0 match of (Lc, Rc) in the handle's mode with (mc, Dc) and
+ *      every other setting unchanged, hole filling off. Median and speckle filters therefore run
+ *      at coarse resolution with unscaled values: a coarse pixel covers four, so a speckle window
+ *      of n coarse pixels removes regions of up to 4 n full-resolution pixels. Its stages are
+ *      profiled under their usual names with the bytes of the coarse geometry.
+ *   4. refine (stage `pyr_refine`): KL, KR are the 24-bit 5x5 census codes of the full-resolution
+ *      grey images (raster over dy = -2..2, dx = -2..2, centre skipped, LSB first; bit =
+ *      I(clamp(y + dy), clamp(x + dx)) < I(y, x)), and h(x, y, d) the sum over j, i in {-1, 0, 1} of
+ *      popcount(KL(cx(x + i), cy(y + j)) ^ KR(cx(x + i - d), cy(y + j))), cx / cy clamping to the
+ *      image. Per pixel, c = C(x >> 1, y >> 1): c == (mc - 1) * 16 gives (m - 1) * 16 (invalid);
+ *      else d0 = (2 c + 8) >> 4 and the candidates d0 + k, k = 0, -1, +1, .. up to +-radius in that
+ *      order, of which those inside [m, m + D - 1] count; the smallest h wins under a strict <
+ *      (none inside: invalid). With sub-pixel on (the census mode's `subpixel`; always in the OCV
+ *      and BM modes) and m < d* < m + D - 1: cm = h(d* - 1), cp = h(d* + 1), c0 = h(d*),
+ *      den = cm + cp - 2 c0, and if cm >= c0, cp >= c0 and den > 0 the offset is
+ *      ((cm - cp) * 16 + den) / (2 den) in C division. out = 16 d* + offset. Columns outside
+ *      [max(m + D, 0), W + min(m, 0)) are invalid.
+ *   5. hole filling, if on, runs last on the full-resolution image: those columns and all rows;
+ *      BM: rows [2 (w / 2), min(H, 2 (Hc - w / 2))).
+ * Like every setter sgm_set_pyramid_params stores any value: a level other than 0 or 1, or at
+ * level 1 a radius outside 1..2, is SGM_ERR_PARAM at match time. At level 1 the full-resolution
+ * parameters are checked as at level 0, except that the mode's range cap applies to Dc
+ * (num_disparities <= 2048 stays for every mode), and every error of the coarse match (BM window
+ * >= min(Wc, Hc), census Dc > 512, ..) is returned with a text naming the coarse geometry; all
+ * errors are decided before any output byte is written. Honoured by sgm_match, sgm_match_f32,
+ * sgm_match_device, sgm_match_device_batch[_rect] (a batch equals n single calls; its coarse frames
+ * go through the level-0 batch in groups of at most 8) and sgm_node_frame, with mono, colour and
+ * raw frames. The two "the WTA writes the float rows itself" shortcuts are not taken at level 1.
+ * sgm_match_batch and the three sgm_match_tiled* calls return SGM_ERR_UNSUPPORTED at level 1 and
+ * write nothing; the sgm_debug_* stage entry points run at level 0 whatever the level (they
+ * still validate the pair like every parameter). sgm_stage_bytes: pyr_down
+ * 2 B/px read, 0.5 B/px of coarse images and 8 B/px of code planes written; pyr_refine 8 B/px of
+ * codes and 0.5 B/px of coarse disparity read, 2 B/px written. Added under ABI version 5 (no
+ * existing struct or signature changed): callers check for the symbols.                          */
+typedef struct sgm_pyramid_params {
+    int level;                /* 0: off; 1: match at half resolution, refine at full resolution   */
+    int radius;               /* level 1: full-resolution disparities searched each side, 1..2    */
+} sgm_pyramid_params;
+/* {0, 2} */
+void sgm_default_pyramid_params(sgm_pyramid_params* p);
+int  sgm_set_pyramid_params(sgm_handle* h, const sgm_pyramid_params* p);
+int  sgm_get_pyramid_params(const sgm_handle* h, sgm_pyramid_params* p);
+/* Validate pyramid parameters without a handle (0 = a match would accept them). Host-only.       */
+int  sgm_check_pyramid_params(const sgm_pyramid_params* p);
+/* The geometry a match of a width x height frame runs its matcher at (host-only, no handle):
+ * out = {Wc, Hc, mc, Dc, invalid_c, invalid}; at level 0 that is {width, height, m, D, invalid,
+ * invalid}. Returns 0, or the error a match would return (bm may be NULL: the BM defaults).      */
+int  sgm_pyramid_plan(const sgm_params* p, const sgm_bm_params* bm, const sgm_pyramid_params* pyr, int width,
+                      int height, int out[6]);
 
 /* ---- colour frames ---------------------------------------------------------------------- */
 /* The node accepts colour cameras: imageCb rectifies whatever encoding arrives
@@ -614,6 +682,16 @@ int  sgm_debug_speckle(sgm_handle* h, int16_t* disp, int width, int height,
 /* sgm_fill_holes on a host int16 image, in place; synchronous.                             */
 int  sgm_debug_fill(sgm_handle* h, int16_t* disp, int width, int height, int invalid,
                     const sgm_fill_params* params, int x0, int y0, int x1, int y1);
+/* The two pyramid kernels on host buffers (synchronous; the handle's pyramid parameters are not
+ * used). sgm_debug_pyr_down: both 8UC1 images halved into ((W + 1) / 2) x ((H + 1) / 2) row-major
+ * images. sgm_debug_pyr_refine: step 4 of the level-1 specification on the full-resolution pair and
+ * a coarse int16 image of that size: m, D the full-resolution range, mc the coarse minimum (its
+ * invalid value is (mc - 1) * 16), radius 1..2 (else SGM_ERR_PARAM); out: W x H int16.           */
+int  sgm_debug_pyr_down(sgm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
+                        size_t stride, uint8_t* out_left, uint8_t* out_right);
+int  sgm_debug_pyr_refine(sgm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
+                          size_t stride, const int16_t* coarse, int m, int D, int mc, int radius, int subpixel,
+                          int16_t* out);
 
 #ifdef __cplusplus
 }
