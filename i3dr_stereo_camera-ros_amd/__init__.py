@@ -191,6 +191,7 @@ EXPORTS = [
     "sgm_debug_bm_plan",
     "sgm_default_pyramid_params", "sgm_set_pyramid_params", "sgm_get_pyramid_params", "sgm_check_pyramid_params",
     "sgm_pyramid_plan", "sgm_debug_pyr_down", "sgm_debug_pyr_refine",
+    "sgm_debug_post",
 ]
 
 
@@ -428,6 +429,10 @@ def load_library(path=None):
     L.sgm_pyramid_plan.argtypes = [P(SgmParams), P(BmParams), P(PyramidParams), ci, ci, P(ci * 6)]
     L.sgm_debug_pyr_down.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp]
     L.sgm_debug_pyr_refine.argtypes = [vp, vp, vp, ci, ci, sz, vp, ci, ci, ci, ci, ci, vp]
+    # ... and the post filters as a match launches them
+    if not hasattr(L, "sgm_debug_post"):
+        raise ImportError(f"{path}: sgm_debug_post is missing: rebuild the library")
+    L.sgm_debug_post.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     _lib = L
     return L
 
@@ -1033,6 +1038,19 @@ class Engine:
         h, w = d.shape
         self._check(self.lib.sgm_debug_speckle(self.h, _ptr(d), w, h, new_val, max_size, max_diff))
         return d
+
+    POST_CANARY = 0x5A5A
+
+    def post(self, disp, median, new_val, max_size, max_diff, out_pad=0):
+        """The post filters as a match launches them (sgm_debug_post): the median alone, the speckle
+        filter alone or the fused median3+speckle, into an image of row stride W + out_pad that starts
+        out as POST_CANARY everywhere. Returns (image[:, :W], pad_columns)."""
+        d = np.ascontiguousarray(disp, np.int16)
+        h, w = d.shape
+        out = np.full((h, w + int(out_pad)), self.POST_CANARY, np.int16)
+        self._check(self.lib.sgm_debug_post(self.h, _ptr(d), w, h, int(out_pad), int(bool(median)), int(new_val),
+                                            int(max_size), int(max_diff), _ptr(out)))
+        return out[:, :w].copy(), out[:, w:].copy()
 
 
 def calc_q(K, P_right, P_left):

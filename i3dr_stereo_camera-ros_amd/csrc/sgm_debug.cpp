@@ -249,6 +249,37 @@ static int debug_post(sgm_handle* h, int16_t* disp, int W, int H, int which, int
 
 int sgm_debug_median3(sgm_handle* h, int16_t* disp, int W, int H) { return debug_post(h, disp, W, H, 0, 0, 0, 0); }
 
+// The post filters launched the way run_post launches them: the raw image at stride W, the result in
+// an image of row stride W + out_pad. `out` comes in holding the caller's canary and goes back whole.
+int sgm_debug_post(sgm_handle* h, const int16_t* disp, int W, int H, int out_pad, int median, int new_val, int max_size,
+                   int max_diff, int16_t* out)
+{
+    if (!h || !disp || !out || W <= 0 || H <= 0 || out_pad < 0) return SGM_ERR_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = ensure_stream(h);
+    if (rc || (rc = order_after_last(h, h->stream))) return rc;
+    const size_t WH = (size_t)W * H, stride = (size_t)W + out_pad, OH = stride * H;
+    const size_t o_dst = align_up(WH * 2), o_lab = o_dst + align_up(OH * 2), o_cnt = o_lab + align_up(WH * 4);
+    if ((rc = ensure_ws(h, o_cnt + align_up(WH * 4)))) return rc;
+    char* ws = (char*)h->ws.base;
+    int16_t* raw = (int16_t*)ws;
+    int16_t* dst = (int16_t*)(ws + o_dst);
+    const bool med = median != 0, spk = max_size > 0;           // use_speckle's rule
+    HIP_TRY(hipMemcpyAsync(dst, out, OH * 2, hipMemcpyHostToDevice, h->stream), "H2D");
+    if (med)
+        HIP_TRY(hipMemcpyAsync(raw, disp, WH * 2, hipMemcpyHostToDevice, h->stream), "H2D");
+    else      // without a median the matcher writes straight into the destination
+        HIP_TRY(hipMemcpy2DAsync(dst, stride * 2, disp, (size_t)W * 2, (size_t)W * 2, H, hipMemcpyHostToDevice,
+                                 h->stream), "H2D");
+    if (med && !spk) HIP_TRY(sgm::launch_median3(raw, W, dst, stride, W, H, h->stream), "median3");
+    if (spk)
+        HIP_TRY(sgm::launch_speckle(med ? raw : nullptr, W, dst, stride, W, H, new_val, max_size, max_diff,
+                                    (int*)(ws + o_lab), (int*)(ws + o_cnt), h->stream), "speckle");
+    HIP_TRY(hipMemcpyAsync(out, dst, OH * 2, hipMemcpyDeviceToHost, h->stream), "D2H");
+    HIP_TRY(hipStreamSynchronize(h->stream), "sync");
+    return SGM_OK;
+}
+
 int sgm_debug_fill(sgm_handle* h, int16_t* disp, int W, int H, int invalid, const sgm_fill_params* params, int x0,
                    int y0, int x1, int y1)
 {

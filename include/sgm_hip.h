@@ -507,7 +507,9 @@ typedef struct sgm_point_xyzrgb { float x, y, z; uint32_t rgba; } sgm_point_xyzr
  *   depth_min/max  the node's depth window (z kept when depth_min <= z <= depth_max)
  *   d_depth    (may be NULL) W x H float depth, 0 where no point
  *   d_points   (may be NULL) the first max_points points in raster order (pcl push_back order)
- *   d_num_points (device int, may be NULL) receives the total number of points.           */
+ *   d_num_points (device int, may be NULL) receives the total number of points.
+ * The per-row counts live in one buffer of the handle whatever `stream` is: calls on one handle
+ * must be ordered by the caller (the same stream, or an event between them).                */
 int  sgm_depth_points(sgm_handle* h, const float* d_disp, size_t disp_stride, int width, int height,
                       const uint8_t* d_color, size_t color_stride, int channels, const double q[5],
                       double depth_min, double depth_max, float* d_depth, size_t depth_stride,
@@ -679,6 +681,14 @@ int  sgm_debug_path_items(const sgm_params* p, int width, int height, unsigned d
 int  sgm_debug_median3(sgm_handle* h, int16_t* disp, int width, int height);
 int  sgm_debug_speckle(sgm_handle* h, int16_t* disp, int width, int height,
                        int new_val, int max_size, int max_diff);
+/* The post filters launched as a match launches them, on host buffers (synchronous): `disp` is the
+ * raw W x H image; `out` has row stride width + out_pad, is uploaded first (so the pad columns keep
+ * whatever the caller put there) and returned whole. median != 0 with max_size <= 0 runs the 3x3
+ * median alone; max_size > 0 runs the speckle filter, with the median fused into its tile kernel
+ * when median != 0; neither copies the image. Added under ABI version 5: callers check for the
+ * symbol.                                                                                     */
+int  sgm_debug_post(sgm_handle* h, const int16_t* disp, int width, int height, int out_pad, int median,
+                    int new_val, int max_size, int max_diff, int16_t* out);
 /* sgm_fill_holes on a host int16 image, in place; synchronous.                             */
 int  sgm_debug_fill(sgm_handle* h, int16_t* disp, int width, int height, int invalid,
                     const sgm_fill_params* params, int x0, int y0, int x1, int y1);
